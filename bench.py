@@ -275,13 +275,19 @@ def verify_transport(ctx, group, reset, transport, iters=3):
     return used, f"{transport} DISAGREED with the host transport and was replaced by {used}"
 
 
-def launch_ranks(n, per_process=1):
+def launch_ranks(n, per_process=1, share_gpu=False):
     """`bench.py --gpus N` invoked plainly: start the ranks as children of this script BEFORE this process has
     touched a GPU (it never does), wait for them, and pass on the worst exit code.  One process per rank, or
     (--ranks-per-process R) one process per R consecutive ranks, each rank a host thread with its own context and
     stream: a rehearsal box admits only a few GPU processes at once.  Rank 0 prints the JSON line on the stdout it
     inherits."""
-    from nbmf_mm_amd import _rendezvous
+    from nbmf_mm_amd import _hip, _rendezvous
+    here_max = min(per_process, n)
+    if share_gpu and here_max > 1 and _hip.hw_queues_at_load() < 2 * here_max:
+        # the ranks of one process wait for each other INSIDE kernels: on one device their streams must not share a
+        # hardware queue, and a process has the queues its environment gives it (two per rank are needed)
+        raise SystemExit(f"--share-gpu with {here_max} ranks per process needs {2 * here_max} hardware queues per process; "
+                         f"the environment gives {_hip.hw_queues_at_load()}")
     import secrets
     port = _rendezvous.free_port()
     secret = os.environ.get("NBMF_RDZV_SECRET") or secrets.token_hex(16)    # only this job's ranks may join its rendezvous
@@ -290,9 +296,6 @@ def launch_ranks(n, per_process=1):
         here = min(per_process, n - r)
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=str(port), NBMF_RDZV_SECRET=secret, NBMF_RANKS_IN_PROCESS=str(here))
-        if here > 1:
-            # the ranks of one process wait for each other INSIDE kernels: their streams must not share a hardware queue
-            env.setdefault("GPU_MAX_HW_QUEUES", str(max(8, 4 * here)))
         procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=env))
     rc = 0
     try:
@@ -360,12 +363,17 @@ def main():
                     help="skip the extra leg that uploads the same V as uint8 (upload.uint8 on the line)")
     ap.add_argument("--no-verify", action="store_true",
                     help="skip the untimed check of the chosen transport against the host transport (--gpus > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed -- the loss curve of the timed call and the factors "
+                         "it left -- as DIR/<name>.npy (float64, at most 64 MB in all: a fixed sample of W's rows beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.overlap:
         os.environ["NBMF_OVERLAP"] = "1"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        raise SystemExit(launch_ranks(args.gpus, max(1, args.ranks_per_process)))   # plain invocation: this process only starts the ranks
+        raise SystemExit(launch_ranks(args.gpus, max(1, args.ranks_per_process), args.share_gpu))   # plain invocation: this process only starts the ranks
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -411,6 +419,30 @@ def main():
         th.join()
     if failed:
         raise SystemExit(1)
+
+
+DUMP_BYTES = 64 << 20     # --dump-outputs: the most it writes, all ranks together
+
+
+def dump_outputs(out_dir, rank, world, r0, losses, W, H):
+    """--dump-outputs: the arrays a caller of the timed path receives after its last step -- the losses of the timed
+    `run` call, and the factors `get_factors` returns then (W as (K, rows of this rank), H as (K, N)) -- as float64 .npy
+    files.  Rank 0 writes `losses` and `H` (H is the same on every rank); every rank writes its rows of W (`W` for one
+    rank, `W_rank<r>` for several).  Where all of W would not fit the budget, each rank writes the columns of a fixed,
+    seeded sample of its rows, and their global row indices as `W_rows` / `W_rows_rank<r>`."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    if rank == 0:
+        np.save(os.path.join(out_dir, "losses.npy"), np.asarray(losses, dtype=np.float64))
+        np.save(os.path.join(out_dir, "H.npy"), np.asarray(H, dtype=np.float64))
+    K, m = W.shape
+    budget = (DUMP_BYTES - (1 << 16) - 8 * (len(losses) + H.size)) // world     # (1 << 16: room for the .npy headers)
+    keep = max(1, budget // (8 * (K + 1)))
+    if keep < m:
+        cols = np.sort(np.random.default_rng([12345, rank]).choice(m, keep, replace=False))
+        np.save(os.path.join(out_dir, f"W_rows{suffix}.npy"), (r0 + cols).astype(np.float64))
+        W = W[:, cols]
+    np.save(os.path.join(out_dir, f"W{suffix}.npy"), np.ascontiguousarray(W, dtype=np.float64))
 
 
 def run_rank(args, rank, local_rank, world):
@@ -541,6 +573,8 @@ def run_rank(args, rank, local_rank, world):
     dt, losses = timed(args.steps)
     tim = ctx.timing()
     ctx.timing_enable(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, r0, losses, *ctx.get_factors())
     h_chunks = ctx.sweep_info()["h_chunks"]
     replicas_identical = None
     devices = group.all_gather(dev_index)

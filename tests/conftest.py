@@ -32,6 +32,14 @@ def golden():
     return load
 
 
+def rank_threads_fit_on_one_gpu(n):
+    """Whether ``n`` rank threads of one process may share one GPU in this environment.  Such ranks wait for each other
+    inside kernels, so their streams need hardware queues of their own: two per rank (nbmf_mm_amd._dist.fit_in_process
+    checks the same).  The tests take the queue count the environment gives the process and never raise it."""
+    from nbmf_mm_amd import _hip
+    return _hip.hw_queues_at_load() >= 2 * n
+
+
 def config1_X():
     return (np.random.default_rng(0).random((100, 500)) < 0.25).astype(np.float64)
 

@@ -8,8 +8,8 @@ UNMEASURED until a machine with several GPUs has run them: they 
 and tolerances as their one-GPU counterparts -- the single-device fit to 1e-12, the replicated factor bitwise equal on
 all ranks, the stop rule at the same iteration.  No device is emulated.
 
-(``NBMF_MULTIDEVICE_REHEARSAL=1 GPU_MAX_HW_QUEUES=32 pytest tests/test_gpu_multidevice.py`` runs the same test BODIES with
-every rank on device 0 -- a rehearsal of the test code itself on a one-GPU box, which proves nothing about devices and is
+(``NBMF_MULTIDEVICE_REHEARSAL=1 pytest tests/test_gpu_multidevice.py``, in an environment that gives a process two hardware
+queues per rank, runs the same test BODIES with every rank on device 0 -- a rehearsal of the test code itself on a one-GPU box, which proves nothing about devices and is
 never on by default; RCCL, which refuses two ranks on one device, is left out of it.)
 
 Reference loop being sharded: src/nbmf_mm/_solver.py:143-175 (the H-step products of :42-43 are what crosses devices)."""
