@@ -37,6 +37,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/nbmf_hip.h"
@@ -88,6 +89,20 @@ int fail(int code, const char* fmt, ...) {
   } while (0)
 
 inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+
+// Environment switches: set at all, or its number (atoll / atof, as the C library parses it) with a default when unset.
+// Each is read where the call that uses it runs (tests switch them between calls), or once per process where a
+// `static const` holds it.
+inline bool env_set(const char* name) { return getenv(name) != nullptr; }
+template <typename T>
+T env_int(const char* name, T dflt) {
+  const char* e = getenv(name);
+  return e ? (T)atoll(e) : dflt;
+}
+inline double env_double(const char* name, double dflt) {
+  const char* e = getenv(name);
+  return e ? atof(e) : dflt;
+}
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -486,10 +501,7 @@ hipError_t dmalloc(T** out, size_t bytes) {
 
 hipError_t dfree(void* p) {
   if (!p) return hipSuccess;
-  static const size_t cap = [] {
-    const char* e = getenv("NBMF_POOL_MB");
-    return (size_t)(e ? std::max(0, atoi(e)) : 1024) << 20;
-  }();
+  static const size_t cap = (size_t)std::max(0, env_int("NBMF_POOL_MB", 1024)) << 20;
   {
     std::lock_guard<std::mutex> lk(g_pool.mu);
     auto it = g_pool.live.find(p);
@@ -565,10 +577,7 @@ void stream_release(int device, hipStream_t st) {   // the caller has synchronis
 hipError_t stream_wait_spin(hipStream_t st, double spin_ms = -1.0) {
   // (the budget: 200 ms unless NBMF_SPIN_MS says otherwise -- a host whose cores are shared by many rank threads may
   //  prefer to sleep at once: NBMF_SPIN_MS=0)
-  static const double spin_default = [] {
-    const char* e = getenv("NBMF_SPIN_MS");
-    return e ? std::max(0.0, atof(e)) : 200.0;
-  }();
+  static const double spin_default = std::max(0.0, env_double("NBMF_SPIN_MS", 200.0));
   if (spin_ms < 0.0) spin_ms = spin_default;
   const auto t0 = std::chrono::steady_clock::now();
   for (;;) {
@@ -619,7 +628,7 @@ int load_rccl() {
   for (const std::string& nm : names) {
     lib = dlopen(nm.c_str(), RTLD_NOW | RTLD_LOCAL);
     if (lib) {
-      if (getenv("NBMF_DEBUG")) fprintf(stderr, "[nbmf] RCCL: %s\n", nm.c_str());
+      if (env_set("NBMF_DEBUG")) fprintf(stderr, "[nbmf] RCCL: %s\n", nm.c_str());
       break;
     }
     tried += nm + " ";
@@ -729,13 +738,12 @@ void arena_release(ArenaSlot* a) {
   if (!a) return;
   std::lock_guard<std::mutex> lk(g_arena_mu);
   a->in_use = false;
-  if (const char* e = getenv("NBMF_ARENA_POOL"))
-    if (atoi(e) == 0) {   // diagnostic: the old behaviour (free on release), to reproduce the stale-mapping failure
-      hipFree(a->arena);
-      hipFree(a->flags);
-      g_arenas.erase(std::find(g_arenas.begin(), g_arenas.end(), a));
-      delete a;
-    }
+  if (env_int("NBMF_ARENA_POOL", 1) == 0) {   // diagnostic: the old behaviour (free on release), to reproduce the stale-mapping failure
+    hipFree(a->arena);
+    hipFree(a->flags);
+    g_arenas.erase(std::find(g_arenas.begin(), g_arenas.end(), a));
+    delete a;
+  }
 }
 
 // ---- the general path's logarithm table: one copy per device and process ------------------------
@@ -775,6 +783,78 @@ hipError_t log_table_device(const double2** out) {
 // takes them.  Sweeps of several launches are bracketed by recorded events as before.
 thread_local hipEvent_t tl_attach_start = nullptr, tl_attach_stop = nullptr;
 std::atomic<long long> g_full_w_launches{0}, g_ragged_launches{0}, g_loss_assembly_recoveries{0};   // nbmf_variant_stats
+
+// NBMF_PASS_TRACE=<n>: every n-th launch of each sweep kernel is traced -- with n > 1 the launches in between run back to
+// back, so the traced one meets the chip in the state a real run leaves it in: clocks under sustained load.  `count` is the
+// kernel's own launch counter.
+bool pass_trace_due(std::atomic<long>& count) {
+  static const int every = env_set("NBMF_PASS_TRACE") ? std::max(1, env_int("NBMF_PASS_TRACE", 1)) : 0;
+  return every && (count.fetch_add(1) % every) == every - 1;
+}
+// The traced launch of pass kernel f (K = 16 KB components): where the workgroups of THIS launch spend their time outside
+// the loop.  Every workgroup notes the wall clock (100 MHz) at entry, at the top of its loop, at the loop's end and at exit;
+// printed: the launch's span, the spread of the entries and exits, mean prologue / loop / epilogue.  Serialises the stream
+// (one launch at a time).
+hipError_t launch_pass_traced(const void* f, dim3 grid, int lds_bytes, hipStream_t st, PassArgs a, int K, int data, int mode) {
+  const size_t n_wg = (size_t)grid.x * grid.y;
+  unsigned long long* tr = nullptr;
+  hipError_t e = dmalloc(&tr, sizeof(unsigned long long) * 8 * n_wg);
+  if (e != hipSuccess) return e;
+  a.trace = tr;
+  void* params[] = {&a};
+  (void)hipLaunchKernel(f, grid, dim3(64 * WG_WAVES), params, lds_bytes, st);
+  std::vector<unsigned long long> h(8 * n_wg);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = hipMemcpy(h.data(), tr, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost);
+  dfree(tr);
+  if (e != hipSuccess) return e;
+  unsigned long long t_first = ~0ull, t_last = 0, last_entry = 0, first_exit = ~0ull;
+  double pro = 0, loop = 0, epi = 0, epi_loss = 0, epi_slab = 0, loop_clk = 0;
+  std::vector<double> exits;
+  size_t live = 0;
+  for (size_t i = 0; i < n_wg; ++i) {
+    const unsigned long long* t = h.data() + 8 * i;
+    if (!t[3]) continue;
+    ++live;
+    t_first = std::min(t_first, t[0]);
+    t_last = std::max(t_last, t[3]);
+    last_entry = std::max(last_entry, t[0]);
+    first_exit = std::min(first_exit, t[3]);
+    pro += (double)(t[1] - t[0]);
+    loop += (double)(t[2] - t[1]);
+    loop_clk += (double)t[7];
+    epi += (double)(t[3] - t[2]);
+    epi_loss += (double)(t[5] - t[2]);
+    epi_slab += (double)(t[6] - t[5]);
+    exits.push_back((double)t[3]);
+  }
+  if (live) {
+    // mean time from entry to exit by the wave slot (HW_ID bits 3:0) the workgroup's first wave was given: does the
+    // SIMD's arbiter favour some slots (oldest first)?
+    double dur[16] = {0};
+    int cnt[16] = {0};
+    for (size_t i = 0; i < n_wg; ++i) {
+      const unsigned long long* t = h.data() + 8 * i;
+      if (!t[3]) continue;
+      dur[t[4] & 15] += (double)(t[3] - t[0]);
+      ++cnt[t[4] & 15];
+    }
+    fprintf(stderr, "[nbmf]   mean entry-to-exit by wave slot:");
+    for (int w = 0; w < 16; ++w)
+      if (cnt[w]) fprintf(stderr, " slot %d: %.1f us (%d)", w, dur[w] / cnt[w] * 0.01, cnt[w]);
+    fprintf(stderr, "\n");
+    std::sort(exits.begin(), exits.end());
+    const double us = 0.01;   // 100 MHz ticks
+    fprintf(stderr, "[nbmf] pass<K=%d,data=%d,mode=%d> %zu workgroups: span %.1f us | entries spread over %.1f us | exits: first %.1f, median %.1f, "
+                    "last %.1f us before the end | per workgroup: prologue %.2f, loop %.2f, epilogue %.2f us (loss block %.2f, slab stores %.2f) | shader clock in the loops %.3f GHz\n", K, data, mode, live,
+            (double)(t_last - t_first) * us, (double)(last_entry - t_first) * us, (double)(t_last - first_exit) * us,
+            ((double)t_last - exits[exits.size() / 2]) * us, 0.0, pro / live * us, loop / live * us, epi / live * us, epi_loss / live * us,
+            epi_slab / live * us, loop > 0 ? loop_clk / loop * 0.1 : 0.0);
+  }
+  return hipSuccess;
+}
+
 template <int KB, int DATA, int MODE, int TH, bool TINY, bool RAG = false, bool FULL = false>
 hipError_t launch_pass_tt(const PassArgs& a_, int chunks, hipStream_t st) {
   if (FULL) g_full_w_launches.fetch_add(1, std::memory_order_relaxed);
@@ -790,71 +870,9 @@ hipError_t launch_pass_tt(const PassArgs& a_, int chunks, hipStream_t st) {
     hipError_t e = log_table_device(&a.ltab_g);
     if (e != hipSuccess) return e;
   }
-  // (NBMF_PASS_TRACE=<n>: every n-th launch of each sweep kernel is traced -- with n > 1 the launches in between run back to
-  //  back, so the traced one meets the chip in the state a real run leaves it in: clocks under sustained load)
-  static const int trace_every = getenv("NBMF_PASS_TRACE") ? std::max(1, atoi(getenv("NBMF_PASS_TRACE"))) : 0;
   static std::atomic<long> trace_count{0};   // (per instantiation)
-  if (trace_every && MODE != MODE_T && (trace_count.fetch_add(1) % trace_every) == trace_every - 1) {
-    // diagnosis: where the workgroups of THIS launch spend their time outside the loop.  Every workgroup notes the wall
-    // clock (100 MHz) at entry, at the top of its loop, at the loop's end and at exit; printed: the launch's span, the
-    // spread of the entries and exits, mean prologue / loop / epilogue.  Serialises the stream (one launch at a time).
-    const size_t n_wg = (size_t)grid.x * grid.y;
-    unsigned long long* tr = nullptr;
-    hipError_t e = dmalloc(&tr, sizeof(unsigned long long) * 8 * n_wg);
-    if (e != hipSuccess) return e;
-    a.trace = tr;
-    hipLaunchKernelGGL((pass_kernel<KB, DATA, MODE, TH, TINY, RAG, FULL>), grid, dim3(64 * WG_WAVES), lds_bytes, st, a);
-    std::vector<unsigned long long> h(8 * n_wg);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = hipMemcpy(h.data(), tr, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost);
-    dfree(tr);
-    if (e != hipSuccess) return e;
-    unsigned long long t_first = ~0ull, t_last = 0, last_entry = 0, first_exit = ~0ull;
-    double pro = 0, loop = 0, epi = 0, epi_loss = 0, epi_slab = 0, loop_clk = 0;
-    std::vector<double> exits;
-    size_t live = 0;
-    for (size_t i = 0; i < n_wg; ++i) {
-      const unsigned long long* t = h.data() + 8 * i;
-      if (!t[3]) continue;
-      ++live;
-      t_first = std::min(t_first, t[0]);
-      t_last = std::max(t_last, t[3]);
-      last_entry = std::max(last_entry, t[0]);
-      first_exit = std::min(first_exit, t[3]);
-      pro += (double)(t[1] - t[0]);
-      loop += (double)(t[2] - t[1]);
-      loop_clk += (double)t[7];
-      epi += (double)(t[3] - t[2]);
-      epi_loss += (double)(t[5] - t[2]);
-      epi_slab += (double)(t[6] - t[5]);
-      exits.push_back((double)t[3]);
-    }
-    if (live) {
-      // mean time from entry to exit by the wave slot (HW_ID bits 3:0) the workgroup's first wave was given: does the
-      // SIMD's arbiter favour some slots (oldest first)?
-      double dur[16] = {0};
-      int cnt[16] = {0};
-      for (size_t i = 0; i < n_wg; ++i) {
-        const unsigned long long* t = h.data() + 8 * i;
-        if (!t[3]) continue;
-        dur[t[4] & 15] += (double)(t[3] - t[0]);
-        ++cnt[t[4] & 15];
-      }
-      fprintf(stderr, "[nbmf]   mean entry-to-exit by wave slot:");
-      for (int w = 0; w < 16; ++w)
-        if (cnt[w]) fprintf(stderr, " slot %d: %.1f us (%d)", w, dur[w] / cnt[w] * 0.01, cnt[w]);
-      fprintf(stderr, "\n");
-      std::sort(exits.begin(), exits.end());
-      const double us = 0.01;   // 100 MHz ticks
-      fprintf(stderr, "[nbmf] pass<K=%d,data=%d,mode=%d> %zu workgroups: span %.1f us | entries spread over %.1f us | exits: first %.1f, median %.1f, "
-                      "last %.1f us before the end | per workgroup: prologue %.2f, loop %.2f, epilogue %.2f us (loss block %.2f, slab stores %.2f) | shader clock in the loops %.3f GHz\n", 16 * KB, DATA, MODE, live,
-              (double)(t_last - t_first) * us, (double)(last_entry - t_first) * us, (double)(t_last - first_exit) * us,
-              ((double)t_last - exits[exits.size() / 2]) * us, 0.0, pro / live * us, loop / live * us, epi / live * us, epi_loss / live * us,
-              epi_slab / live * us, loop > 0 ? loop_clk / loop * 0.1 : 0.0);
-    }
-    return hipSuccess;
-  }
+  if (MODE != MODE_T && pass_trace_due(trace_count))
+    return launch_pass_traced((const void*)pass_kernel<KB, DATA, MODE, TH, TINY, RAG, FULL>, grid, lds_bytes, st, a, 16 * KB, DATA, MODE);
   if (tl_attach_start) {
     hipEvent_t e0 = tl_attach_start, e1 = tl_attach_stop;
     tl_attach_start = tl_attach_stop = nullptr;
@@ -878,9 +896,9 @@ hipError_t launch_pass_t(const PassArgs& a, int chunks, hipStream_t st) {
   // W sweeps over a matrix that is observed everywhere and has no pad rows in the swept dimension: the two-state variant
   // (FULL, nbmf_pass_kernel.inc; NBMF_NO_FULL_W=1: the three-state kernels on such data -- tests)
   constexpr bool HAS_FULL = TH == 0 && MODE == MODE_W && DATA == DATA_BIN;
-  static const bool no_full = getenv("NBMF_NO_FULL_W") != nullptr;
+  static const bool no_full = env_set("NBMF_NO_FULL_W");
   const bool full = HAS_FULL && a.full && !no_full;
-  static const bool no_rag = getenv("NBMF_NO_RAGGED_K") != nullptr;   // (tests: the full-K kernels on a ragged K -- the same bits)
+  static const bool no_rag = env_set("NBMF_NO_RAGGED_K");   // (tests: the full-K kernels on a ragged K -- the same bits)
   if (HAS_RAG && !no_rag && a.ksteps > 0 && a.ksteps < 4 * KB) {
     const int per_block = MODE == MODE_H ? 8 : (MODE == MODE_W ? 4 : 0);   // back-product MFMAs of one 16-block of components
     const int skipped = (4 * KB - a.ksteps) + (KB >= 4 ? (KB - a.kblocks) * per_block : 0);
@@ -908,53 +926,41 @@ inline hipError_t launch_theta(const PassArgs& a, int chunks, hipStream_t st) {
   return launch_pass_t<8, DATA_BIN, MODE_T, 0>(a, chunks, st);
 }
 
-template <int DATA, int MODE>
-hipError_t launch_pass_kb(int KB, const PassArgs& a, int chunks, hipStream_t st) {
-  switch (KB) {
-    case 1: return launch_pass_t<1, DATA, MODE>(a, chunks, st);
-    case 2: return launch_pass_t<2, DATA, MODE>(a, chunks, st);
-    case 4: return launch_pass_t<4, DATA, MODE>(a, chunks, st);
-    case 8: return launch_pass_t<8, DATA, MODE>(a, chunks, st);
+// The (KB, data kind) pairs the sweep kernels are built for: f(integral_constant KB, integral_constant DATA), or `none`
+// for a pair that is not one of them
+template <typename R, typename F>
+R pass_dispatch(int KB, int data_kind, R none, F f) {
+  auto by_kb = [&](auto data) -> R {
+    switch (KB) {
+      case 1: return f(std::integral_constant<int, 1>{}, data);
+      case 2: return f(std::integral_constant<int, 2>{}, data);
+      case 4: return f(std::integral_constant<int, 4>{}, data);
+      case 8: return f(std::integral_constant<int, 8>{}, data);
+    }
+    return none;
+  };
+  switch (data_kind) {
+    case DATA_BIN: return by_kb(std::integral_constant<int, DATA_BIN>{});
+    case DATA_F64: return by_kb(std::integral_constant<int, DATA_F64>{});
+    case DATA_F64M: return by_kb(std::integral_constant<int, DATA_F64M>{});
   }
-  return hipErrorInvalidValue;
+  return none;
 }
 
 template <int MODE>
 hipError_t launch_pass(int KB, int data_kind, const PassArgs& a, int chunks, hipStream_t st) {
-  switch (data_kind) {
-    case DATA_BIN: return launch_pass_kb<DATA_BIN, MODE>(KB, a, chunks, st);
-    case DATA_F64: return launch_pass_kb<DATA_F64, MODE>(KB, a, chunks, st);
-    case DATA_F64M: return launch_pass_kb<DATA_F64M, MODE>(KB, a, chunks, st);
-  }
-  return hipErrorInvalidValue;
-}
-
-template <int DATA, int MODE>
-const void* pass_ptr_kb(int KB) {
-  switch (KB) {
-    case 1: return (const void*)pass_kernel<1, DATA, MODE>;
-    case 2: return (const void*)pass_kernel<2, DATA, MODE>;
-    case 4: return (const void*)pass_kernel<4, DATA, MODE>;
-    case 8: return (const void*)pass_kernel<8, DATA, MODE>;
-  }
-  return nullptr;
-}
-
-template <int MODE>
-const void* pass_ptr(int KB, int data_kind) {
-  switch (data_kind) {
-    case DATA_BIN: return pass_ptr_kb<DATA_BIN, MODE>(KB);
-    case DATA_F64: return pass_ptr_kb<DATA_F64, MODE>(KB);
-    case DATA_F64M: return pass_ptr_kb<DATA_F64M, MODE>(KB);
-  }
-  return nullptr;
+  return pass_dispatch(KB, data_kind, hipErrorInvalidValue, [&](auto kb, auto data) -> hipError_t {
+    return launch_pass_t<decltype(kb)::value, decltype(data)::value, MODE>(a, chunks, st);
+  });
 }
 
 // workgroups of this pass kernel that one CU holds at once (registers and LDS decide)
 template <int MODE>
 int resident_per_cu(int KB, int data_kind) {
   int n = 0;
-  const void* f = pass_ptr<MODE>(KB, data_kind);
+  const void* f = pass_dispatch(KB, data_kind, (const void*)nullptr, [](auto kb, auto data) -> const void* {
+    return (const void*)pass_kernel<decltype(kb)::value, decltype(data)::value, MODE>;
+  });
   const int lds_bytes = pass_lds_bytes(KB, data_kind, MODE);
   if (!f || hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 64 * WG_WAVES, lds_bytes) != hipSuccess || n < 1) n = 2;
   return std::min(n, 8);
@@ -968,10 +974,10 @@ int resident_per_cu(int KB, int data_kind) {
 // NBMF_TARGET_WGS=<n> overrides the target (tuning experiments only).
 void pick_chunks(int strips_groups, int Rb, int NB, int slots, int ns, int cus, bool one_round_ok, int* chunks, int* CH) {
   (void)slots;
-  int target = 2048;
-  const char* te = getenv(one_round_ok ? "NBMF_TARGET_WGS_H" : "NBMF_TARGET_WGS_W");   // (tuning experiments: one sweep only)
-  if (!te) te = getenv("NBMF_TARGET_WGS");
-  if (te) target = std::max(1, atoi(te));
+  const char* target_var = one_round_ok ? "NBMF_TARGET_WGS_H" : "NBMF_TARGET_WGS_W";   // (tuning experiments: one sweep only)
+  if (!env_set(target_var)) target_var = "NBMF_TARGET_WGS";
+  const bool target_set = env_set(target_var);
+  const int target = std::max(1, env_int(target_var, 2048));
   int want = (target + strips_groups - 1) / strips_groups;
   const int max_chunks = std::max(1, Rb / NB);
   want = std::min(std::max(want, 1), max_chunks);
@@ -982,7 +988,7 @@ void pick_chunks(int strips_groups, int Rb, int NB, int slots, int ns, int cus, 
   //  perplexity grid on the lastfm-sized matrix 0.63 -> 0.33 s.)
   // (ns = strips per wave: a workgroup of the two-strip kernels does a 64-block sweep's work in 32 blocks)
   int min_blocks = (long long)strips_groups * ns * ((Rb + 63) / 64) >= 512 ? 64 / ns : 8;
-  if (const char* e = getenv("NBMF_MIN_BLOCKS")) min_blocks = std::max(NB, atoi(e));   // (tuning experiments only)
+  if (env_set("NBMF_MIN_BLOCKS")) min_blocks = std::max(NB, env_int("NBMF_MIN_BLOCKS", 0));   // (tuning experiments only)
   const bool clipped = ch < std::min(Rb, min_blocks);   // the sweep is too short for the target at min_blocks per chunk
   ch = std::max(ch, std::min(Rb, min_blocks));
   ch = (int)round_up(ch, NB);
@@ -992,7 +998,7 @@ void pick_chunks(int strips_groups, int Rb, int NB, int slots, int ns, int cus, 
   // 4.16 rounds -- a fifth round for 80 workgroups, MFMA-busy 84 %.  More chunks are tried (up to four times as many,
   // whole multiples of 8 first: the XCD renumbering of pass_kernel wants those) until the rounds are >= 95 % full.
   // The sweeps of configs[1..3] and of their shards already are (2048 or 1024 workgroups: 4 or 2 full rounds).
-  if (cus > 0 && !te && !getenv("NBMF_MIN_BLOCKS") && !getenv("NBMF_NO_ROUND_FILL")) {
+  if (cus > 0 && !target_set && !env_set("NBMF_MIN_BLOCKS") && !env_set("NBMF_NO_ROUND_FILL")) {
     const long long places = (long long)cus * std::min(std::max(slots / cus, 1), 2);
     auto fill = [&](int blocks_per_chunk) {   // how full the rounds are with chunks of that many row blocks
       const long long wgs = (long long)strips_groups * ((Rb + blocks_per_chunk - 1) / blocks_per_chunk);
@@ -1054,7 +1060,7 @@ struct EvScope {
   // count = false: add the time to `kind` but do not count a launch (second part of a split sweep)
   // attach = true: the scope holds exactly one pass launch, on c->stream, which carries the events itself (launch_pass_tt)
   EvScope(nbmf_ctx* c_, int kind_, bool count = true, bool attach_ = false)
-      : c(c_), kind(kind_ | (count ? 0 : 0x100)), attach(attach_ && !getenv("NBMF_TIMING_BRACKET")) {
+      : c(c_), kind(kind_ | (count ? 0 : 0x100)), attach(attach_ && !env_set("NBMF_TIMING_BRACKET")) {
     if (!c->timing || (c->timing_stride > 1 && c->timing_it % c->timing_stride != 0)) return;
     if (c->ev_used + 2 > c->ev.size()) {
       for (int i = 0; i < 2; ++i) {
@@ -1113,7 +1119,7 @@ int all_reduce_inplace(nbmf_ctx* c, double* p, size_t count, hipStream_t st = nu
     const unsigned grid = (unsigned)std::min<long long>(128, std::max<long long>(1, (slice + 1023) / 1024));
     // (fault injection for the tests of the failure path: NBMF_PEER_FAULT=1 makes the LAST rank skip its part of
     //  every generic exchange, as a rank whose links do not work would -- the others must time out, not hang)
-    static const bool fault = getenv("NBMF_PEER_FAULT") && atoi(getenv("NBMF_PEER_FAULT")) != 0;
+    static const bool fault = env_int("NBMF_PEER_FAULT", 0) != 0;
     if (!(fault && c->pv.nranks > 1 && c->pv.rank == c->pv.nranks - 1))
       hipLaunchKernelGGL(peer_reduce_kernel, dim3(grid), dim3(256), 0, s, c->pv, e, off, (long long)count, c->flags);
     HIPCHK(hipGetLastError());
@@ -1219,17 +1225,76 @@ int enqueue_exchange_after_sweep(nbmf_ctx* c, const PassArgs& a, bool with_produ
   return NBMF_OK;
 }
 
+// The two sweeps' arguments over all K_pad components: the sweep over image A (H-pass; the likelihood sweeps take it
+// with their own mode bits) and the one over image B (W-pass)
+PassArgs h_pass_args(nbmf_ctx* c) {
+  PassArgs a{};
+  a.data = sweep_image(c, 0);
+  a.mask = c->maskA;
+  a.LT = c->WT;
+  a.LG = c->WG;
+  a.RfT = c->HT;
+  a.out1 = c->slabH;
+  a.out2 = c->slabH + (size_t)c->chunksH * c->KP * c->nA;
+  a.lossbuf = c->lossbuf;
+  a.done = c->flags;
+  a.Rb = (int)(c->mA / 16);
+  a.Cb = (int)(c->nA / 16);
+  a.chunk_start = c->cstartH;
+  a.C_alloc = c->nA;
+  a.eps = c->eps;
+  a.tiny_eps = tiny_a(c);
+  a.ksteps = (c->k + 3) / 4;
+  a.kblocks = (c->k + 15) / 16;
+  return a;
+}
+PassArgs w_pass_args(nbmf_ctx* c) {
+  PassArgs a{};
+  a.data = sweep_image(c, 1);
+  a.mask = c->maskB;
+  a.LT = c->HT;
+  a.LG = c->HG;
+  a.RfT = c->WT;
+  a.out1 = c->slabW;
+  a.out2 = nullptr;
+  a.lossbuf = nullptr;
+  a.done = c->flags;
+  a.Rb = (int)(c->nA / 16);
+  a.Cb = (int)(c->mA / 16);
+  a.chunk_start = c->cstartW;
+  a.C_alloc = c->mA;
+  a.eps = c->eps;
+  a.tiny_eps = tiny_a(c) || c->w_free;   // (transform's W steps start from a W that is not on the simplex: the select variant)
+  // every entry observed (no mask, or a mask of ones); pad rows of the dimension the W sweep walks (the columns of Y) would
+  // count as observed zeros in the two-state variant's column sums: there are none, or they are "ones" in image B's lane
+  // masks (mark_pad_rows_b)
+  a.full = c->data_kind == DATA_BIN && c->n_obs == (double)c->m * (double)c->n && (c->nA == c->n || c->padB_ones);
+  a.ksteps = (c->k + 3) / 4;
+  a.kblocks = (c->k + 15) / 16;
+  return a;
+}
+
+// Point a sweep over image `image` (0: A, 1: B) at slice sl of the components: its factor operands and, where it writes
+// them, its slabs (slice-major: the chunks of slice 0, then those of slice 1, ...; out2 of image A behind all KS slices'
+// out1).
+void at_slice(const nbmf_ctx* c, PassArgs& a, int image, int sl) {
+  const size_t offW = (size_t)sl * SLICE_K * c->mA, offH = (size_t)sl * SLICE_K * c->nA;
+  a.LT = image == 0 ? c->WT + offW : c->HT + offH;
+  a.LG = image == 0 ? c->WG + offW : c->HG + offH;
+  a.RfT = image == 0 ? c->HT + offH : c->WT + offW;
+  const size_t slab_off = image == 0 ? (size_t)c->chunksH * offH : (size_t)c->chunksW * offW;
+  if (a.out1) a.out1 += slab_off;
+  if (a.out2) a.out2 += slab_off;
+}
+
 // ---- n_components > 128: slices of SLICE_K components --------------------------------
 // Theta of the current factors WITHOUT the last slice's part into c->theta, in the tile order of image A (image
 // 0: H-pass and loglik sweeps) or image B (image 1: W-pass): one Theta-only sweep per slice, each adding onto the
 // previous ones.
 int enqueue_theta(nbmf_ctx* c, int image) {
   for (int sl = 0; sl < c->KS - 1; ++sl) {   // (the last slice's part is added by that slice's own fused sweep)
-    const size_t offW = (size_t)sl * SLICE_K * c->mA, offH = (size_t)sl * SLICE_K * c->nA;
     PassArgs a{};
-    a.LT = image == 0 ? c->WT + offW : c->HT + offH;
-    a.LG = image == 0 ? c->WG + offW : c->HG + offH;   // not read by this mode
-    a.RfT = image == 0 ? c->HT + offH : c->WT + offW;
+    at_slice(c, a, image, sl);   // (LG is not read by this mode; no slabs)
     a.theta = c->theta;
     a.accum = sl > 0;
     a.done = c->flags;
@@ -1250,28 +1315,12 @@ int enqueue_theta(nbmf_ctx* c, int image) {
 // read the total.  (Theta crosses HBM 24 KS - 16 bytes per entry instead of 24 KS - 8, in one sweep fewer.)
 int enqueue_a_sweeps_sliced(nbmf_ctx* c, bool with_products, int strict, int clip) {
   if (int rc = enqueue_theta(c, 0)) return rc;
-  const size_t per = (size_t)SLICE_K * c->nA;
   const int last = c->KS - 1;
   for (int step = 0; step < (with_products ? c->KS : 1); ++step) {
     const int sl = step == 0 ? last : step - 1;
-    PassArgs a{};
-    a.data = sweep_image(c, 0);
-    a.mask = c->maskA;
-    a.LT = c->WT + (size_t)sl * SLICE_K * c->mA;
-    a.LG = c->WG + (size_t)sl * SLICE_K * c->mA;
-    a.RfT = c->HT + (size_t)sl * SLICE_K * c->nA;
-    a.out1 = c->slabH + (size_t)sl * c->chunksH * per;
-    a.out2 = c->slabH + (size_t)(c->KS + sl) * c->chunksH * per;
-    a.lossbuf = step == 0 ? c->lossbuf : nullptr;   // the likelihood is the same in every slice's sweep
-    a.done = c->flags;
-    a.Rb = (int)(c->mA / 16);
-    a.Cb = (int)(c->nA / 16);
-    a.chunk_start = c->cstartH;
-    a.C_alloc = c->nA;
-    a.eps = c->eps;
-    a.tiny_eps = tiny_a(c);
-    a.ksteps = (c->k + 3) / 4;
-    a.kblocks = (c->k + 15) / 16;
+    PassArgs a = h_pass_args(c);
+    at_slice(c, a, 0, sl);
+    if (step != 0) a.lossbuf = nullptr;   // the likelihood is the same in every slice's sweep
     a.strict = strict;
     a.clip = clip;
     a.theta = c->theta;
@@ -1300,17 +1349,17 @@ int fill_ll_empty(nbmf_ctx* c) {
   HIPCHK(hipGetLastError());
   return NBMF_OK;
 }
-bool fin_fusable(const nbmf_ctx* c) { return !is_sharded(c) && c->KS == 1 && !getenv("NBMF_NO_FUSED_FINALIZE"); }
+bool fin_fusable(const nbmf_ctx* c) { return !is_sharded(c) && c->KS == 1 && !env_set("NBMF_NO_FUSED_FINALIZE"); }
 void fin_fill(nbmf_ctx* c, PassArgs& a, int t, double tol, int strict) {
   a.fin.on = 1;
   a.fin.wait_ticks = LL_WAIT_TICKS;
-  if (const char* e = getenv("NBMF_PASSFIN_FAULT"))   // tests: one workgroup withholds its partial, the wait is short
-    if (atoi(e) == 2) {
-      a.fin.wait_ticks = 0;             // (2: nobody withholds anything, but the assembling workgroup does not wait at all -- it
-    } else if (atoi(e) != 0) {          //  gives up while other workgroups of its sweep are still running, as under a tenant)
-      a.fin.on = 2;
-      a.fin.wait_ticks = 20000000ull;   // 0.2 s
-    }
+  const int fault = env_int("NBMF_PASSFIN_FAULT", 0);   // tests: one workgroup withholds its partial, the wait is short
+  if (fault == 2) {
+    a.fin.wait_ticks = 0;             // (2: nobody withholds anything, but the assembling workgroup does not wait at all -- it
+  } else if (fault != 0) {            //  gives up while other workgroups of its sweep are still running, as under a tenant)
+    a.fin.on = 2;
+    a.fin.wait_ticks = 20000000ull;   // 0.2 s
+  }
   a.lossbuf = c->lossfin;   // (the sweep's workgroups hand their partials in here; see PassFin)
   a.fin.t = t;
   a.fin.n_ll = c->chunksH * (int)(c->nA / 16 / wg_strips(c));
@@ -1326,77 +1375,31 @@ void fin_fill(nbmf_ctx* c, PassArgs& a, int t, double tol, int strict) {
   a.fin.flags = c->flags;
 }
 
-// fin_t >= 0 (and fin_fusable): also the loss and stop test of iteration fin_t, in the sweep's last workgroup
-int enqueue_h_pass(nbmf_ctx* c, int fin_t = -1, double tol = 0.0) {
+// The sweep over image A: with_products, the H-pass; without, the Theta-only sweep -- the log-likelihood of the current
+// factors at a third of the H-pass's MFMA work, its per-wave partials in lossbuf exactly as an H-pass leaves them.
+// fin_t >= 0 (and fin_fusable): also the loss and stop test of iteration fin_t, in the sweep's last workgroup.
+int enqueue_a_sweep(nbmf_ctx* c, bool with_products, int strict = 0, int clip = 0, int fin_t = -1, double tol = 0.0) {
+  PassArgs a = h_pass_args(c);
   if (c->KS > 1) {
-    {
+    if (with_products) {
       EvScope ev(c, 0);
       if (int rc = enqueue_a_sweeps_sliced(c, true, 0, 0)) return rc;
+    } else {
+      if (int rc = enqueue_a_sweeps_sliced(c, false, strict, clip)) return rc;
     }
-    PassArgs a{};
-    a.Cb = (int)(c->nA / 16);
-    return enqueue_exchange_after_sweep(c, a, /*with_products=*/true, /*strict=*/0);
+    return enqueue_exchange_after_sweep(c, a, with_products, strict);
   }
-  PassArgs a{};
-  a.data = sweep_image(c, 0);
-  a.mask = c->maskA;
-  a.LT = c->WT;
-  a.LG = c->WG;
-  a.RfT = c->HT;
-  a.out1 = c->slabH;
-  a.out2 = c->slabH + (size_t)c->chunksH * c->KP * c->nA;
-  a.lossbuf = c->lossbuf;
-  a.done = c->flags;
-  a.Rb = (int)(c->mA / 16);
-  a.Cb = (int)(c->nA / 16);
-  a.chunk_start = c->cstartH;
-  a.C_alloc = c->nA;
-  a.eps = c->eps;
-  a.tiny_eps = tiny_a(c);
-  a.ksteps = (c->k + 3) / 4;
-  a.kblocks = (c->k + 15) / 16;
-  if (fin_t >= 0) fin_fill(c, a, fin_t, tol, 0);
-  {
-    EvScope ev(c, 0, true, /*attach=*/true);
-    HIPCHK(launch_pass<MODE_H>(c->KB, c->data_kind, a, c->chunksH, c->stream));
-  }
-  if (int rc = enqueue_exchange_after_sweep(c, a, /*with_products=*/true, /*strict=*/0)) return rc;
-  return NBMF_OK;
-}
-
-// Theta-only sweep (no back-products): the log-likelihood of the current factors at a third of the
-// H-pass's MFMA work; the per-wave partials land in lossbuf exactly as an H-pass leaves them.
-int enqueue_loglik_pass(nbmf_ctx* c, int strict, int clip = 0, int fin_t = -1, double tol = 0.0) {
-  if (c->KS > 1) {
-    if (int rc = enqueue_a_sweeps_sliced(c, false, strict, clip)) return rc;
-    PassArgs a{};
-    a.Cb = (int)(c->nA / 16);
-    return enqueue_exchange_after_sweep(c, a, /*with_products=*/false, strict);
-  }
-  PassArgs a{};
-  a.data = sweep_image(c, 0);
-  a.mask = c->maskA;
-  a.LT = c->WT;
-  a.LG = c->WG;
-  a.RfT = c->HT;
-  a.out1 = c->slabH;      // unused
-  a.out2 = nullptr;
-  a.lossbuf = c->lossbuf;
-  a.done = c->flags;
-  a.Rb = (int)(c->mA / 16);
-  a.Cb = (int)(c->nA / 16);
-  a.chunk_start = c->cstartH;
-  a.C_alloc = c->nA;
-  a.eps = c->eps;
-  a.tiny_eps = tiny_a(c);
-  a.ksteps = (c->k + 3) / 4;
-  a.kblocks = (c->k + 15) / 16;
   a.strict = strict;
   a.clip = clip;
+  if (!with_products) a.out2 = nullptr;   // (out1 unused)
   if (fin_t >= 0) fin_fill(c, a, fin_t, tol, strict);
-  HIPCHK(launch_pass<MODE_L>(c->KB, c->data_kind, a, c->chunksH, c->stream));
-  if (int rc = enqueue_exchange_after_sweep(c, a, /*with_products=*/false, strict)) return rc;
-  return NBMF_OK;
+  if (with_products) {
+    EvScope ev(c, 0, true, /*attach=*/true);
+    HIPCHK(launch_pass<MODE_H>(c->KB, c->data_kind, a, c->chunksH, c->stream));
+  } else {
+    HIPCHK(launch_pass<MODE_L>(c->KB, c->data_kind, a, c->chunksH, c->stream));
+  }
+  return enqueue_exchange_after_sweep(c, a, with_products, strict);
 }
 
 int enqueue_finalize(nbmf_ctx* c, int t, double tol, bool loglik_only = false, int strict = 0) {
@@ -1416,62 +1419,53 @@ int enqueue_finalize(nbmf_ctx* c, int t, double tol, bool loglik_only = false, i
   return NBMF_OK;
 }
 
-int enqueue_h_update(nbmf_ctx* c) {
-  if (c->KS > 1) {
-    // the update is elementwise in k: one launch per slice on that slice's rows of H and its slabs
-    const size_t per = (size_t)SLICE_K * c->nA;
-    const int blocks = (int)(per / 256);
-    for (int sl = 0; sl < c->KS; ++sl) {
-      const int ks = std::min(SLICE_K, c->k - sl * SLICE_K);
-      hipLaunchKernelGGL(h_update_kernel, dim3(blocks), dim3(256), 0, c->stream,
-                         (const double*)(c->slabH + (size_t)sl * c->chunksH * per),
-                         (const double*)(c->slabH + (size_t)(c->KS + sl) * c->chunksH * per), c->chunksH, per, (long long)c->nA, 0LL,
-                         0LL, (long long)c->nA, c->Hn + sl * per, c->HT + sl * per, c->HG + sl * per,
-                         c->prior + 2 * (size_t)sl * blocks, ks, SLICE_K, (long long)c->n, (long long)c->nA, c->alpha - 1.0,
-                         c->beta - 1.0, c->eps, c->flags, pform_inv12(c));
-      HIPCHK(hipGetLastError());
-    }
-    c->prior_src = c->prior;
-    c->n_prior_src = c->n_prior_blocks;
-    return NBMF_OK;
+// The products of the H-pass as every H-step source holds them: [P1 | P2], each half `chunks` partial sums
+// [chunks][KP][wp] of the columns [c0, c0 + wp) (the slabs: chunksH sums, all nA columns; the exchanged sums: one, of a
+// panel or of all columns), a slice's rows of a half at chunks x (its first row) x wp.
+//
+// H-update (h_update_kernel) of slice sl's rows of H, columns [c0, c0 + wp), from the sources at src (its slice, P1 half)
+// whose partial sums lie chunk_stride doubles apart.  Grid and prior-sum pairs: one per 256 entries of the slice's KSK
+// rows, from entry KSK (sl nA + c0) on.  The blocks are whole: KSK is 16 KB or SLICE_K, nA a multiple of 128, a panel's c0
+// and wp multiples of 16.  For all columns of an unsliced run the grid is therefore KP nA / 256 = n_prior_blocks.
+void launch_h_update(nbmf_ctx* c, const double* src, int chunks, size_t chunk_stride, long long c0, long long wp, int sl,
+                     double pform, hipStream_t st) {
+  const int KSK = std::min(c->KP, SLICE_K);
+  const size_t per = (size_t)KSK * c->nA;
+  const long long blk0 = (long long)KSK * (sl * c->nA + c0) / 256;
+  hipLaunchKernelGGL(h_update_kernel, dim3((unsigned)((long long)KSK * wp / 256)), dim3(256), 0, st, src,
+                     src + (size_t)chunks * c->KP * wp, chunks, chunk_stride, wp, c0, c0, wp, c->Hn + sl * per, c->HT + sl * per,
+                     c->HG + sl * per, c->prior + 2 * (size_t)blk0, std::min(KSK, c->k - sl * KSK), KSK, (long long)c->n,
+                     (long long)c->nA, c->alpha - 1.0, c->beta - 1.0, c->eps, c->flags, pform);
+}
+
+// Ordered sum (reduce_h_kernel) of slice sl's H-pass slabs, columns [c0, c0 + wp), into [P1 | P2] at dst (rows dst_ld
+// apart, P2 KP rows behind P1) in the form P1, P2 themselves; ll_dst not null: the log-likelihood partials, summed, there.
+void launch_reduce_h(nbmf_ctx* c, int sl, long long c0, long long wp, double* dst, long long dst_ld, double* ll_dst, hipStream_t st) {
+  const int KSK = std::min(c->KP, SLICE_K);
+  const size_t per = (size_t)KSK * c->nA;
+  const int n_loss = c->chunksH * (int)(c->nA / 16 / wg_strips(c));
+  hipLaunchKernelGGL(reduce_h_kernel, dim3((unsigned)(((long long)KSK * wp + 255) / 256)), dim3(256), 0, st,
+                     (const double*)(c->slabH + (size_t)sl * c->chunksH * per),
+                     (const double*)(c->slabH + (size_t)(c->KS + sl) * c->chunksH * per), c->chunksH, (long long)per,
+                     (long long)c->nA, c0, wp, dst_ld, KSK, dst, dst + (size_t)c->KP * dst_ld, (const double*)c->lossbuf, n_loss,
+                     ll_pad_of(c), ll_dst, c->flags, pform_inv12(c));
+}
+
+// H-update of all columns, one launch per slice, from [P1 | P2] at `src`: the H-pass slabs (slabs: in the form
+// pform_inv12), or the products summed over chunks and ranks (P1, P2 themselves: reduce_h_kernel)
+int enqueue_h_update_from(nbmf_ctx* c, const double* src, bool slabs, hipStream_t st) {
+  const size_t per = (size_t)std::min(c->KP, SLICE_K) * c->nA;
+  const int chunks = slabs ? c->chunksH : 1;
+  for (int sl = 0; sl < c->KS; ++sl) {
+    launch_h_update(c, src + (size_t)sl * chunks * per, chunks, slabs ? per : 0, 0, c->nA, sl, slabs ? pform_inv12(c) : 0.0, st);
+    HIPCHK(hipGetLastError());
   }
-  // single GPU or column split: sum the H-pass slabs here, all columns in one launch
-  const size_t per = (size_t)c->KP * c->nA;
-  hipLaunchKernelGGL(h_update_kernel, dim3(c->n_prior_blocks), dim3(256), 0, c->stream, (const double*)c->slabH,
-                     (const double*)(c->slabH + (size_t)c->chunksH * per), c->chunksH, per, (long long)c->nA, 0LL, 0LL,
-                     (long long)c->nA, c->Hn, c->HT, c->HG, c->prior, c->k, c->KP, (long long)c->n, (long long)c->nA,
-                     c->alpha - 1.0, c->beta - 1.0, c->eps, c->flags, pform_inv12(c));
-  HIPCHK(hipGetLastError());
   c->prior_src = c->prior;
   c->n_prior_src = c->n_prior_blocks;
   return NBMF_OK;
 }
-
-PassArgs w_pass_args(nbmf_ctx* c) {
-  PassArgs a{};
-  a.data = sweep_image(c, 1);
-  a.mask = c->maskB;
-  a.LT = c->HT;
-  a.LG = c->HG;
-  a.RfT = c->WT;
-  a.out1 = c->slabW;
-  a.out2 = nullptr;
-  a.lossbuf = nullptr;
-  a.done = c->flags;
-  a.Rb = (int)(c->nA / 16);
-  a.Cb = (int)(c->mA / 16);
-  a.chunk_start = c->cstartW;
-  a.C_alloc = c->mA;
-  a.eps = c->eps;
-  a.tiny_eps = tiny_a(c) || c->w_free;   // (transform's W steps start from a W that is not on the simplex: the select variant)
-  // every entry observed (no mask, or a mask of ones); pad rows of the dimension the W sweep walks (the columns of Y) would
-  // count as observed zeros in the two-state variant's column sums: there are none, or they are "ones" in image B's lane
-  // masks (mark_pad_rows_b)
-  a.full = c->data_kind == DATA_BIN && c->n_obs == (double)c->m * (double)c->n && (c->nA == c->n || c->padB_ones);
-  a.ksteps = (c->k + 3) / 4;
-  a.kblocks = (c->k + 15) / 16;
-  return a;
-}
+// (single GPU or column split: the update is elementwise in k -- one launch per slice on that slice's rows and slabs)
+int enqueue_h_update(nbmf_ctx* c) { return enqueue_h_update_from(c, c->slabH, /*slabs=*/true, c->stream); }
 
 template <int GROUPS>
 int launch_w_update(nbmf_ctx* c, const double* q, int chunks, double n_div, int projection) {
@@ -1494,35 +1488,11 @@ int enqueue_w_update(nbmf_ctx* c, const double* q, int chunks, double n_div, int
 // Rows of Y split: ordered sum of the H-pass slabs into [P1 | P2 | loglik] at `dst` (natural [KP][nA] twice);
 // with slices, one launch per slice on its rows.
 int enqueue_reduce_h_all(nbmf_ctx* c, double* dst, hipStream_t st) {
-  const int KSK = std::min(c->KP, SLICE_K);
-  const size_t per = (size_t)KSK * c->nA, tot = (size_t)c->KP * c->nA;
-  const int n_loss = c->chunksH * (int)(c->nA / 16 / wg_strips(c));
+  const size_t per = (size_t)std::min(c->KP, SLICE_K) * c->nA, tot = (size_t)c->KP * c->nA;
   for (int sl = 0; sl < c->KS; ++sl) {
-    hipLaunchKernelGGL(reduce_h_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st,
-                       (const double*)(c->slabH + (size_t)sl * c->chunksH * per),
-                       (const double*)(c->slabH + (size_t)(c->KS + sl) * c->chunksH * per), c->chunksH, (long long)per,
-                       (long long)c->nA, 0LL, (long long)c->nA, (long long)c->nA, KSK, dst + sl * per, dst + tot + sl * per,
-                       (const double*)c->lossbuf, n_loss, ll_pad_of(c), sl == 0 ? dst + 2 * tot : (double*)nullptr, c->flags, pform_inv12(c));
+    launch_reduce_h(c, sl, 0, c->nA, dst + sl * per, c->nA, sl == 0 ? dst + 2 * tot : (double*)nullptr, st);
     HIPCHK(hipGetLastError());
   }
-  return NBMF_OK;
-}
-
-// H-update of all columns from the summed products at `src` ([P1 | P2], natural), one launch per slice
-int enqueue_h_update_from(nbmf_ctx* c, const double* src, hipStream_t st) {
-  const int KSK = std::min(c->KP, SLICE_K);
-  const size_t per = (size_t)KSK * c->nA, tot = (size_t)c->KP * c->nA;
-  const int blocks = (int)(per / 256);
-  for (int sl = 0; sl < c->KS; ++sl) {
-    const int ks = std::min(KSK, c->k - sl * KSK);
-    hipLaunchKernelGGL(h_update_kernel, dim3(blocks), dim3(256), 0, st, src + sl * per, src + tot + sl * per, 1, (size_t)0,
-                       (long long)c->nA, 0LL, 0LL, (long long)c->nA, c->Hn + sl * per, c->HT + sl * per, c->HG + sl * per,
-                       c->prior + 2 * (size_t)sl * blocks, ks, KSK, (long long)c->n, (long long)c->nA, c->alpha - 1.0,
-                       c->beta - 1.0, c->eps, c->flags, /*pform=*/0.0);   // (the exchanged sums are P1, P2 themselves: reduce_h_kernel)
-    HIPCHK(hipGetLastError());
-  }
-  c->prior_src = c->prior;
-  c->n_prior_src = c->n_prior_blocks;
   return NBMF_OK;
 }
 
@@ -1536,30 +1506,12 @@ int enqueue_w_step(nbmf_ctx* c, int projection);
 //   factors stay those of iteration it-1, as in the single-GPU run) -> W-pass -> W-update.
 int enqueue_iteration_rows_peer(nbmf_ctx* c, int it, double tol) {
   const size_t per = (size_t)c->KP * c->nA;
-  PassArgs a{};
-  a.data = sweep_image(c, 0);
-  a.mask = c->maskA;
-  a.LT = c->WT;
-  a.LG = c->WG;
-  a.RfT = c->HT;
-  a.out1 = c->slabH;
-  a.out2 = c->slabH + (size_t)c->chunksH * per;
-  a.lossbuf = c->lossbuf;
-  a.done = c->flags;
-  a.Rb = (int)(c->mA / 16);
-  a.Cb = (int)(c->nA / 16);
-  a.chunk_start = c->cstartH;
-  a.C_alloc = c->nA;
-  a.eps = c->eps;
-  a.tiny_eps = tiny_a(c);
-  a.ksteps = (c->k + 3) / 4;
-  a.kblocks = (c->k + 15) / 16;
   {
     EvScope ev(c, 0, true, /*attach=*/c->KS == 1);
     if (c->KS > 1) {
       if (int rc = enqueue_a_sweeps_sliced(c, true, 0, 0)) return rc;
     } else {
-      HIPCHK(launch_pass<MODE_H>(c->KB, c->data_kind, a, c->chunksH, c->stream));
+      HIPCHK(launch_pass<MODE_H>(c->KB, c->data_kind, h_pass_args(c), c->chunksH, c->stream));
     }
   }
   double* X = c->arena;   // [P1 (KP x nA) | P2 (KP x nA) | loglik], natural order
@@ -1572,7 +1524,6 @@ int enqueue_iteration_rows_peer(nbmf_ctx* c, int it, double tol) {
   const long long offPR_prev = c->prior_src ? (long long)(c->prior_src - c->arena) : 0;
   const bool prev_in_arena = c->prior_src >= c->arena && c->prior_src < c->arena + c->arena_doubles;
   const int fin_t = (it > 0 && prev_in_arena) ? it - 1 : -1;
-  const int n_loss = c->chunksH * (a.Cb / wg_strips(c));
   // One column panel [pc0[p], pc0[p+1]) of the H-step on stream `st`: ordered slab sum into the arena, then the
   // fused reduce-scatter + Beta-MAP update + broadcast of this rank's slice of the panel (flag slot p).
   auto exchange_panel = [&](int p, hipStream_t st, unsigned long long e) -> int {
@@ -1580,10 +1531,7 @@ int enqueue_iteration_rows_peer(nbmf_ctx* c, int it, double tol) {
     if (c->KS > 1) {
       if (int rc = enqueue_reduce_h_all(c, X, st)) return rc;   // (slices: one panel, see comm_finish_init)
     } else {
-      hipLaunchKernelGGL(reduce_h_kernel, dim3((unsigned)(((long long)c->KP * wp + 255) / 256)), dim3(256), 0, st,
-                         (const double*)a.out1, (const double*)a.out2, c->chunksH, (long long)per, (long long)c->nA, c0, wp,
-                         (long long)c->nA, c->KP, X + c0, X + per + c0, (const double*)c->lossbuf, n_loss, ll_pad_of(c),
-                         p == 0 ? X + 2 * per : (double*)nullptr, c->flags, pform_inv12(c));
+      launch_reduce_h(c, 0, c0, wp, X + c0, c->nA, p == 0 ? X + 2 * per : (double*)nullptr, st);
       HIPCHK(hipGetLastError());
     }
     PeerView pv = c->pv;
@@ -1662,56 +1610,28 @@ int enqueue_iteration_rows(nbmf_ctx* c, int it, double tol) {
     c->ll_ptr = c->Pbuf + 2 * tot;
     if (it > 0)
       if (int rc = enqueue_finalize(c, it - 1, tol)) return rc;
-    if (int rc = enqueue_h_update_from(c, c->Pbuf, c->stream)) return rc;
+    if (int rc = enqueue_h_update_from(c, c->Pbuf, /*slabs=*/false, c->stream)) return rc;
     return enqueue_w_step(c, c->projection);
   }
   hipStream_t s0 = c->stream;
   const bool two_streams = c->npanel == 2 && c->comm && c->stream2;
   hipStream_t s1 = two_streams ? c->stream2 : s0;
-  const size_t per = (size_t)c->KP * c->nA;
   // ---- H-pass (all columns)
-  PassArgs a{};
-  a.data = sweep_image(c, 0);
-  a.mask = c->maskA;
-  a.LT = c->WT;
-  a.LG = c->WG;
-  a.RfT = c->HT;
-  a.out1 = c->slabH;
-  a.out2 = c->slabH + (size_t)c->chunksH * per;
-  a.lossbuf = c->lossbuf;
-  a.done = c->flags;
-  a.Rb = (int)(c->mA / 16);
-  a.Cb = (int)(c->nA / 16);
-  a.chunk_start = c->cstartH;
-  a.C_alloc = c->nA;
-  a.eps = c->eps;
-  a.tiny_eps = tiny_a(c);
-  a.ksteps = (c->k + 3) / 4;
-  a.kblocks = (c->k + 15) / 16;
   {
     EvScope ev(c, 0, true, /*attach=*/true);
-    HIPCHK(launch_pass<MODE_H>(c->KB, c->data_kind, a, c->chunksH, s0));
+    HIPCHK(launch_pass<MODE_H>(c->KB, c->data_kind, h_pass_args(c), c->chunksH, s0));
   }
   if (two_streams) HIPCHK(hipEventRecord(c->evH, s0));
-  const int n_loss = c->chunksH * (a.Cb / wg_strips(c));
   auto reduce_panel = [&](int p, hipStream_t st) -> int {
     const long long c0 = c->pc0[p], wp = c->pc0[p + 1] - c0;
     double* d1 = c->Pbuf + c->pbase[p];
-    double* d2 = d1 + (size_t)c->KP * wp;
-    hipLaunchKernelGGL(reduce_h_kernel, dim3((unsigned)(((long long)c->KP * wp + 255) / 256)), dim3(256), 0, st,
-                       (const double*)a.out1, (const double*)a.out2, c->chunksH, (long long)per, (long long)c->nA, c0, wp, wp,
-                       c->KP, d1, d2, (const double*)c->lossbuf, n_loss, ll_pad_of(c),
-                       p == 0 ? c->Pbuf + c->ll_index : (double*)nullptr, c->flags, pform_inv12(c));
+    launch_reduce_h(c, 0, c0, wp, d1, wp, p == 0 ? c->Pbuf + c->ll_index : (double*)nullptr, st);
     HIPCHK(hipGetLastError());
     return all_reduce_inplace(c, d1, 2 * (size_t)c->KP * wp + (p == 0 ? 1 : 0), st);
   };
   auto update_panel = [&](int p, hipStream_t st) -> int {
     const long long c0 = c->pc0[p], wp = c->pc0[p + 1] - c0;
-    const double* d1 = c->Pbuf + c->pbase[p];
-    const unsigned blk0 = (unsigned)((long long)c->KP * c0 / 256);
-    hipLaunchKernelGGL(h_update_kernel, dim3((unsigned)((long long)c->KP * wp / 256)), dim3(256), 0, st, d1,
-                       d1 + (size_t)c->KP * wp, 1, (size_t)0, wp, c0, c0, wp, c->Hn, c->HT, c->HG, c->prior + 2 * (size_t)blk0,
-                       c->k, c->KP, (long long)c->n, (long long)c->nA, c->alpha - 1.0, c->beta - 1.0, c->eps, c->flags, /*pform=*/0.0);
+    launch_h_update(c, c->Pbuf + c->pbase[p], 1, 0, c0, wp, 0, /*pform=*/0.0, st);   // (the exchanged sums: P1, P2 themselves)
     HIPCHK(hipGetLastError());
     c->prior_src = c->prior;
     c->n_prior_src = c->n_prior_blocks;
@@ -1764,10 +1684,7 @@ int enqueue_w_step(nbmf_ctx* c, int projection) {
       for (int step = 0; step < c->KS; ++step) {   // the last slice first: it completes and stores Theta'
         const int sl = step == 0 ? c->KS - 1 : step - 1;
         PassArgs w = w_pass_args(c);
-        w.LT = c->HT + (size_t)sl * SLICE_K * c->nA;
-        w.LG = c->HG + (size_t)sl * SLICE_K * c->nA;
-        w.RfT = c->WT + (size_t)sl * SLICE_K * c->mA;
-        w.out1 = c->slabW + (size_t)sl * c->chunksW * SLICE_K * c->mA;
+        at_slice(c, w, 1, sl);
         w.theta = c->theta;
         if (step == 0)
           HIPCHK((launch_pass_slice<MODE_W, 2>(c->data_kind, w, c->chunksW, c->stream)));
@@ -1821,16 +1738,23 @@ __global__ void expand_factor_kernel(const double* __restrict__ Fn, double* __re
   FG[g_index(k, x, KS, lenA)] = Fn[idx];
 }
 
-template <int KB, bool SPLIT, bool BATCH>
-const void* small_ptr(int data_kind) {
-  switch (data_kind) {
-    case DATA_BIN: return (const void*)small_fit_kernel<KB, DATA_BIN, SPLIT, BATCH>;
-    case DATA_F64: return (const void*)small_fit_kernel<KB, DATA_F64, SPLIT, BATCH>;
-    case DATA_F64M: return (const void*)small_fit_kernel<KB, DATA_F64M, SPLIT, BATCH>;
-  }
-  return nullptr;
+// The factor launches on the context's stream, for W (h = false: lengths m, mA) or H (h = true: n, nA).  set: natural
+// [k][len] at src -> padded natural [KP][lenA] and its T and G images (slice width min(KP, SLICE_K): KP in every unsliced
+// run, the single-launch engine's included); get: the other way; expand: the context's own natural factor -> its images.
+void launch_set_factor(const nbmf_ctx* c, bool h, const double* src, double* Fn, double* FT, double* FG) {
+  const long long len = h ? c->n : c->m, lenA = h ? c->nA : c->mA, tot = (long long)c->KP * lenA;
+  hipLaunchKernelGGL(set_factor_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, src, Fn, FT, FG, c->k, c->KP,
+                     std::min(c->KP, SLICE_K), len, lenA);
 }
-const void* small_kernel_for(const nbmf_ctx* c, bool split, bool batch);
+void launch_get_factor(const nbmf_ctx* c, bool h, const double* Fn, double* dst) {
+  const long long len = h ? c->n : c->m, lenA = h ? c->nA : c->mA, tot = (long long)c->k * len;
+  hipLaunchKernelGGL(get_factor_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, Fn, dst, c->k, len, lenA);
+}
+void launch_expand_factor(const nbmf_ctx* c, bool h) {
+  const long long lenA = h ? c->nA : c->mA, tot = (long long)c->KP * lenA;
+  hipLaunchKernelGGL(expand_factor_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, (const double*)(h ? c->Hn : c->Wn),
+                     h ? c->HT : c->WT, h ? c->HG : c->WG, c->KP, c->KP, lenA);
+}
 
 // How many workgroups a strip of the H-step (sweep of Rbe blocks, Cbe strips) or of the W-step is split over: aim at
 // two tiles per wave, stay within the CUs, at most 8 parts (one partner hand-off costs ~2 us: not worth it for
@@ -1853,11 +1777,9 @@ bool small_eligible(const nbmf_ctx* c, int cus) {
   //  it, in the same batches -- so a verbose fit and a silent one give the same bits)
   if (is_sharded(c) || c->KS != 1 || c->KB > 2 || c->timing) return false;
   cus = std::min(cus, SMALL_MAX_WGS);   // a device reporting more CUs than the buffers were sized for uses that many of them
-  if (const char* e = getenv("NBMF_PERSISTENT"))
-    if (atoi(e) == 0) return false;
+  if (env_int("NBMF_PERSISTENT", 1) == 0) return false;
   const long long Rbe = (c->m + 15) / 16, Cbe = (c->n + 15) / 16;
-  long long max_tiles = 32768;
-  if (const char* e = getenv("NBMF_SMALL_TILES")) max_tiles = atoll(e);
+  const long long max_tiles = env_int("NBMF_SMALL_TILES", 32768LL);
   const int NW = sm_waves(c->KB), PH = small_parts(c, Rbe, Cbe), PW = small_parts(c, Cbe, Rbe);
   const bool fits = (Rbe + (long long)PH * NW - 1) / ((long long)PH * NW) <= SM_TPW && (Cbe + (long long)PW * NW - 1) / ((long long)PW * NW) <= SM_TPW;
   if (!(fits && Cbe <= 128 && Cbe * PH <= cus && Rbe * PW <= cus && Rbe * Cbe <= max_tiles)) return false;
@@ -1937,12 +1859,34 @@ int small_prepare(nbmf_ctx* c) {
   return NBMF_OK;
 }
 
-const void* small_kernel_for(const nbmf_ctx* c, bool split, bool batch) {
-  if (c->KB == 1)
-    return batch ? (split ? small_ptr<1, true, true>(c->data_kind) : small_ptr<1, false, true>(c->data_kind))
-                 : (split ? small_ptr<1, true, false>(c->data_kind) : small_ptr<1, false, false>(c->data_kind));
-  return batch ? (split ? small_ptr<2, true, true>(c->data_kind) : small_ptr<2, false, true>(c->data_kind))
-               : (split ? small_ptr<2, true, false>(c->data_kind) : small_ptr<2, false, false>(c->data_kind));
+// The single-launch kernel of a run (split: strips over several workgroups; batch: nbmf_run_batch), its waves per
+// workgroup and dynamic LDS, with the attribute that allows that much; k->f stays null if no kernel is built for the context.
+struct SmallKernel {
+  const void* f = nullptr;
+  int NW = 0;
+  size_t lds_bytes = 0;
+};
+template <int KB, bool SPLIT, bool BATCH>
+const void* small_ptr(int data_kind) {
+  switch (data_kind) {
+    case DATA_BIN: return (const void*)small_fit_kernel<KB, DATA_BIN, SPLIT, BATCH>;
+    case DATA_F64: return (const void*)small_fit_kernel<KB, DATA_F64, SPLIT, BATCH>;
+    case DATA_F64M: return (const void*)small_fit_kernel<KB, DATA_F64M, SPLIT, BATCH>;
+  }
+  return nullptr;
+}
+template <int KB>
+const void* small_ptr(int data_kind, bool split, bool batch) {
+  if (batch) return split ? small_ptr<KB, true, true>(data_kind) : small_ptr<KB, false, true>(data_kind);
+  return split ? small_ptr<KB, true, false>(data_kind) : small_ptr<KB, false, false>(data_kind);
+}
+int small_kernel(const nbmf_ctx* c, bool split, bool batch, SmallKernel* k) {
+  k->f = c->KB == 1 ? small_ptr<1>(c->data_kind, split, batch) : small_ptr<2>(c->data_kind, split, batch);
+  if (!k->f) return NBMF_OK;
+  k->NW = sm_waves(c->KB);
+  k->lds_bytes = sizeof(double) * ((size_t)k->NW * 2 * c->KB * 4 * 64 + k->NW * 16 + 64 + 2 * c->KP * 16) + LOG_TABLE_BYTES;
+  HIPCHK(hipFuncSetAttribute(k->f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k->lds_bytes));
+  return NBMF_OK;
 }
 
 // Everything in SmallArgs that a run shares with every other run on this context's data: the packed images, the
@@ -1982,10 +1926,8 @@ void small_common_args(const nbmf_ctx* c, int max_iter, double tol, SmallArgs* o
   a.n_obs = c->n_obs_global;
   a.n_div = (double)c->n;
   a.ll_pad = (256.0 * a.Rbe * a.Cbe - (double)c->m * (double)c->n) * log(1.0 + c->eps);
-  double ms = 2000.0;
-  if (const char* e = getenv("NBMF_SMALL_TIMEOUT_MS")) ms = std::max(1.0, atof(e));
-  a.timeout = (unsigned long long)(ms * 1e5);
-  if (const char* e = getenv("NBMF_SMALL_FENCED")) a.fenced = atoi(e) != 0;   // release / acquire around every hand-off (nbmf_small_kernel.inc: small_arrive)
+  a.timeout = (unsigned long long)(std::max(1.0, env_double("NBMF_SMALL_TIMEOUT_MS", 2000.0)) * 1e5);
+  a.fenced = env_int("NBMF_SMALL_FENCED", 0) != 0;   // release / acquire around every hand-off (nbmf_small_kernel.inc: small_arrive)
 }
 
 // END-OF-RUN GUARD of the single-launch engine (round 6).  Its hand-offs are the guide's measured sc1 form, not the memory
@@ -1999,19 +1941,39 @@ void small_common_args(const nbmf_ctx* c, int max_iter, double tol, SmallArgs* o
 // (nbmf_engine_stats: gave_up).  NBMF_SMALL_GUARD=0 switches the check off; NBMF_SMALL_GUARD_FAULT=1 (tests) makes it trip.
 int loss_by_launches(nbmf_ctx* c, double* out);
 bool small_guard_on() {
-  static const bool on = !(getenv("NBMF_SMALL_GUARD") && atoi(getenv("NBMF_SMALL_GUARD")) == 0);
+  static const bool on = env_int("NBMF_SMALL_GUARD", 1) != 0;
   return on;
 }
 int small_guard(nbmf_ctx* c, double reported, bool* ok) {
   double chk = 0.0;
   if (int rc = loss_by_launches(c, &chk)) return rc;
-  if (getenv("NBMF_SMALL_GUARD_FAULT")) chk += 1e-6 * std::fabs(chk) + 1e-300;
+  if (env_set("NBMF_SMALL_GUARD_FAULT")) chk += 1e-6 * std::fabs(chk) + 1e-300;
   *ok = (std::isnan(chk) && std::isnan(reported)) || chk == reported ||
         std::fabs(chk - reported) <= 1e-12 * std::max(std::fabs(chk), std::fabs(reported));
-  if (!*ok && getenv("NBMF_DEBUG"))
+  if (!*ok && env_set("NBMF_DEBUG"))
     fprintf(stderr, "[nbmf] single-launch guard: reported loss %.17g, recomputed %.17g: redone by the launches\n", reported, chk);
   return NBMF_OK;
 }
+
+// A single-launch run that gave up, counted (nbmf_small_stats, nbmf_engine_stats); disable: a barrier was abandoned,
+// and the context keeps to the launches from now on.  fmt: what NBMF_DEBUG prints.
+void small_give_up(nbmf_ctx* c, bool disable, const char* fmt = nullptr, ...) {
+  ++c->small.aborted;
+  g_engine_persistent_aborted.fetch_add(1, std::memory_order_relaxed);
+  if (disable) c->small.disabled = true;
+  if (fmt && env_set("NBMF_DEBUG")) {
+    va_list ap;
+    va_start(ap, fmt);
+    vfprintf(stderr, fmt, ap);
+    va_end(ap);
+  }
+}
+
+// Synchronises a stream when it goes out of scope, whichever way the function returns
+struct DrainGuard {
+  hipStream_t st;
+  ~DrainGuard() { hipStreamSynchronize(st); }
+};
 
 // Returns NBMF_OK with *handled = true when the run is complete (losses, n_iter filled, factors in the context's
 // buffers); *handled = false means "use the five-kernel path" (factors restored to their state at entry).
@@ -2033,19 +1995,16 @@ int run_small(nbmf_ctx* c, int max_iter, double tol, double* losses, int* n_iter
   a.part_buf = w.part_buf;
   a.part_ll = w.part_ll;
   a.part_flag = w.part_flag;
-  const bool split = a.PH > 1 || a.PW > 1;
-  const void* f = small_kernel_for(c, split, false);
-  if (!f) return NBMF_OK;
-  const int NW = sm_waves(c->KB);
-  const size_t lds_bytes = sizeof(double) * ((size_t)NW * 2 * c->KB * 4 * 64 + NW * 16 + 64 + 2 * c->KP * 16) + LOG_TABLE_BYTES;
-  HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  SmallKernel k;
+  if (int rc = small_kernel(c, a.PH > 1 || a.PW > 1, /*batch=*/false, &k)) return rc;
+  if (!k.f) return NBMF_OK;
   // snapshot for the fall-back, hand-off words cleared
   HIPCHK(hipMemcpyAsync(w.snapW, c->Wn, fw, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(w.snapH, c->Hn, fh, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(hipMemsetAsync(w.sync, 0, sizeof(unsigned long long) * (a.G + 1), c->stream));
   HIPCHK(hipMemsetAsync(w.part_flag, 0, sizeof(unsigned long long) * SMALL_MAX_WGS, c->stream));
   HIPCHK(hipMemsetAsync(w.result, 0, sizeof(int) * 4, c->stream));
-  if (getenv("NBMF_SMALL_FORCE_ABORT")) {   // tests: raise the abort word up front, so that the fall-back runs
+  if (env_set("NBMF_SMALL_FORCE_ABORT")) {   // tests: raise the abort word up front, so that the fall-back runs
     const unsigned long long one = 1;
     HIPCHK(hipMemcpyAsync(w.sync + a.G, &one, sizeof one, hipMemcpyHostToDevice, c->stream));
   }
@@ -2061,22 +2020,19 @@ int run_small(nbmf_ctx* c, int max_iter, double tol, double* losses, int* n_iter
       if (b) dfree(b);
     }
   } diag_guard{dbg, place};
-  if (getenv("NBMF_SMALL_DEBUG")) {
+  if (env_set("NBMF_SMALL_DEBUG")) {
     HIPCHK(dmalloc(&dbg, sizeof(unsigned long long) * 64 * 16));
     HIPCHK(hipMemsetAsync(dbg, 0, sizeof(unsigned long long) * 64 * 16, c->stream));
     a.dbg = dbg;
   }
-  if (getenv("NBMF_SMALL_PLACEMENT")) {
+  if (env_set("NBMF_SMALL_PLACEMENT")) {
     HIPCHK(dmalloc(&place, sizeof(unsigned long long) * a.G));
     a.place = place;
   }
   void* params[] = {&a};
   SmallReservation cus_held(c->device, a.G, std::min(c->cus, SMALL_MAX_WGS));
-  struct DrainGuard {
-    hipStream_t st;
-    ~DrainGuard() { hipStreamSynchronize(st); }
-  } drain_guard{c->stream};
-  HIPCHK(hipLaunchKernel(f, dim3(a.G), dim3(64 * NW), params, lds_bytes, c->stream));
+  DrainGuard drain_guard{c->stream};
+  HIPCHK(hipLaunchKernel(k.f, dim3(a.G), dim3(64 * k.NW), params, k.lds_bytes, c->stream));
   if (place) {   // where the dispatcher put the workgroups: XCD . shader engine . CU
     std::vector<unsigned long long> h(a.G);
     HIPCHK(hipMemcpyAsync(h.data(), place, sizeof(unsigned long long) * a.G, hipMemcpyDeviceToHost, c->stream));
@@ -2126,18 +2082,12 @@ int run_small(nbmf_ctx* c, int max_iter, double tol, double* losses, int* n_iter
   HIPCHK(hipMemcpyAsync(&abort_word, w.sync + a.G, sizeof abort_word, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(stream_wait_spin(c->stream));
   ++w.runs;
-  auto back_to_entry = [&](bool disable) -> int {
-    ++w.aborted;
-    g_engine_persistent_aborted.fetch_add(1, std::memory_order_relaxed);
-    if (disable) w.disabled = true;
+  auto back_to_entry = [&]() -> int {   // (after small_give_up)
     HIPCHK(hipMemcpyAsync(c->Wn, w.snapW, fw, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->Hn, w.snapH, fh, hipMemcpyDeviceToDevice, c->stream));
-    const long long tw = (long long)c->KP * c->mA, th = (long long)c->KP * c->nA;
-    hipLaunchKernelGGL(expand_factor_kernel, dim3((unsigned)((tw + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->Wn,
-                       c->WT, c->WG, c->KP, c->KP, (long long)c->mA);
+    launch_expand_factor(c, /*h=*/false);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(expand_factor_kernel, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->Hn,
-                       c->HT, c->HG, c->KP, c->KP, (long long)c->nA);
+    launch_expand_factor(c, /*h=*/true);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
     return NBMF_OK;
@@ -2145,8 +2095,8 @@ int run_small(nbmf_ctx* c, int max_iter, double tol, double* losses, int* n_iter
   if (res[2] != 0 || abort_word != 0 || res[0] < 1 || res[0] > max_iter) {
     // a barrier was abandoned (workgroups not co-resident for too long): back to the state at entry, and this
     // context keeps to the five-kernel path from now on
-    if (getenv("NBMF_DEBUG")) fprintf(stderr, "[nbmf] persistent fit abandoned (status %d, abort word %llu): five-kernel path\n", res[2], abort_word);
-    return back_to_entry(/*disable=*/true);
+    small_give_up(c, /*disable=*/true, "[nbmf] persistent fit abandoned (status %d, abort word %llu): five-kernel path\n", res[2], abort_word);
+    return back_to_entry();
   }
   if (res[1] == 0) {   // the final factors sit in the second set of images
     HIPCHK(hipMemcpyAsync(c->Wn, w.Wn, fw, hipMemcpyDeviceToDevice, c->stream));
@@ -2161,7 +2111,10 @@ int run_small(nbmf_ctx* c, int max_iter, double tol, double* losses, int* n_iter
   if (small_guard_on()) {   // (see small_guard: the last loss as reported against the loss of the factors as they are in memory)
     bool ok = true;
     if (int rc = small_guard(c, losses[res[0] - 1], &ok)) return rc;
-    if (!ok) return back_to_entry(/*disable=*/false);   // *handled stays false: the launches redo the run from the state at entry
+    if (!ok) {   // *handled stays false: the launches redo the run from the state at entry
+      small_give_up(c, /*disable=*/false);
+      return back_to_entry();
+    }
   }
   *n_iter = res[0];
   *handled = true;
@@ -2236,17 +2189,14 @@ int run_small_batch(nbmf_ctx* c, int nprob, const double* alpha, const double* b
   small_common_args(c, max_iter, tol, &a);
   const int cap_cus = std::min(c->cus, SMALL_MAX_WGS);
   int B = std::max(1, cap_cus / a.G);
-  if (const char* e = getenv("NBMF_BATCH_MAX")) B = std::max(1, std::min(B, atoi(e)));
+  B = std::max(1, std::min(B, env_int("NBMF_BATCH_MAX", B)));   // (B >= 1 already: unset changes nothing)
   B = std::min(B, nprob);
   if (int rc = small_batch_prepare(c, B, max_iter)) return rc;
   auto& b = c->small_batch;
   const SmallBatchLayout L = small_batch_layout(c, b.losses_cap);
-  const bool split = a.PH > 1 || a.PW > 1;
-  const void* f = small_kernel_for(c, split, true);
-  if (!f) return NBMF_OK;
-  const int NW = sm_waves(c->KB);
-  const size_t lds_bytes = sizeof(double) * ((size_t)NW * 2 * c->KB * 4 * 64 + NW * 16 + 64 + 2 * c->KP * 16) + LOG_TABLE_BYTES;
-  HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  SmallKernel k;
+  if (int rc = small_kernel(c, a.PH > 1 || a.PW > 1, /*batch=*/true, &k)) return rc;
+  if (!k.f) return NBMF_OK;
   const size_t wsz = (size_t)c->k * c->m, hsz = (size_t)c->k * c->n;
   // problem 0's pointers; problem p's are these plus p * stride (PP() in the kernel, prob() here)
   {
@@ -2287,27 +2237,20 @@ int run_small_batch(nbmf_ctx* c, int nprob, const double* alpha, const double* b
     HIPCHK(hipMemcpyAsync(b.io, W0 + (size_t)p0 * wsz, sizeof(double) * wsz * Bc, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b.io + wsz * Bc, H0 + (size_t)p0 * hsz, sizeof(double) * hsz * Bc, hipMemcpyHostToDevice, c->stream));
     for (int p = 0; p < Bc; ++p) {
-      const long long tw = (long long)c->KP * c->mA, th = (long long)c->KP * c->nA;
-      hipLaunchKernelGGL(set_factor_kernel, dim3((unsigned)((tw + 255) / 256)), dim3(256), 0, c->stream, (const double*)(b.io + wsz * p),
-                         prob(a.Wn[1], p), prob(a.WT[1], p), prob(a.WG[1], p), c->k, c->KP, c->KP, (long long)c->m, (long long)c->mA);
-      hipLaunchKernelGGL(set_factor_kernel, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, c->stream,
-                         (const double*)(b.io + wsz * Bc + hsz * p), prob(a.Hn[1], p), prob(a.HT[1], p), prob(a.HG[1], p), c->k, c->KP,
-                         c->KP, (long long)c->n, (long long)c->nA);
+      launch_set_factor(c, /*h=*/false, b.io + wsz * p, prob(a.Wn[1], p), prob(a.WT[1], p), prob(a.WG[1], p));
+      launch_set_factor(c, /*h=*/true, b.io + wsz * Bc + hsz * p, prob(a.Hn[1], p), prob(a.HT[1], p), prob(a.HG[1], p));
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemset2DAsync(b.slab + L.off_control, L.stride, 0, L.control, (size_t)Bc, c->stream));   // every problem's control words
-    if (getenv("NBMF_SMALL_FORCE_ABORT")) {   // tests: the abort word of the first problem up front
+    if (env_set("NBMF_SMALL_FORCE_ABORT")) {   // tests: the abort word of the first problem up front
       const unsigned long long one = 1;
       HIPCHK(hipMemcpyAsync(a.sync + a.G, &one, sizeof one, hipMemcpyHostToDevice, c->stream));
     }
     void* params[] = {&a};
     {
       SmallReservation cus_held(c->device, a.G * Bc, cap_cus);
-      struct DrainGuard {
-        hipStream_t st;
-        ~DrainGuard() { hipStreamSynchronize(st); }
-      } drain_guard{c->stream};
-      HIPCHK(hipLaunchKernel(f, dim3(a.G, Bc), dim3(64 * NW), params, lds_bytes, c->stream));
+      DrainGuard drain_guard{c->stream};
+      HIPCHK(hipLaunchKernel(k.f, dim3(a.G, Bc), dim3(64 * k.NW), params, k.lds_bytes, c->stream));
       // results and abort words of all problems: strided copies
       HIPCHK(hipMemcpy2DAsync(res.data(), sizeof(int) * 4, a.result, L.stride, sizeof(int) * 4, (size_t)Bc, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(hipMemcpy2DAsync(abort_words.data(), sizeof(unsigned long long), a.sync + a.G, L.stride, sizeof(unsigned long long), (size_t)Bc,
@@ -2318,10 +2261,7 @@ int run_small_batch(nbmf_ctx* c, int nprob, const double* alpha, const double* b
     b.problems += Bc;
     for (int p = 0; p < Bc; ++p)
       if (res[(size_t)p * 4 + 2] != 0 || abort_words[(size_t)p] != 0 || res[(size_t)p * 4] < 1 || res[(size_t)p * 4] > max_iter) {
-        c->small.disabled = true;   // a barrier was abandoned: this context keeps to the launches from now on
-        ++c->small.aborted;
-        g_engine_persistent_aborted.fetch_add(1, std::memory_order_relaxed);
-        if (getenv("NBMF_DEBUG")) fprintf(stderr, "[nbmf] batched persistent fit abandoned (problem %d): one by one\n", p0 + p);
+        small_give_up(c, /*disable=*/true, "[nbmf] batched persistent fit abandoned (problem %d): one by one\n", p0 + p);
         return NBMF_OK;             // *handled stays false: the caller redoes ALL problems one by one
       }
     // the end-of-run guard (small_guard), on ONE problem of every launch, taken in turn: its last reported loss against the
@@ -2348,19 +2288,15 @@ int run_small_batch(nbmf_ctx* c, int nprob, const double* alpha, const double* b
       bool ok = true;
       if (int rc = small_guard(c, reported, &ok)) return rc;
       if (!ok) {
-        ++c->small.aborted;
-        g_engine_persistent_aborted.fetch_add(1, std::memory_order_relaxed);
+        small_give_up(c, /*disable=*/false);
         return NBMF_OK;             // *handled stays false: the caller redoes ALL problems one by one, by the launches
       }
     }
     // results: final factors (the parity each problem ended on) through one staging copy, the loss curves in one strided copy
     for (int p = 0; p < Bc; ++p) {
       const int par = res[(size_t)p * 4 + 1];
-      const long long tw = (long long)c->k * c->m, th = (long long)c->k * c->n;
-      hipLaunchKernelGGL(get_factor_kernel, dim3((unsigned)((tw + 255) / 256)), dim3(256), 0, c->stream, (const double*)prob(a.Wn[par], p),
-                         b.io + wsz * p, c->k, (long long)c->m, (long long)c->mA);
-      hipLaunchKernelGGL(get_factor_kernel, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, c->stream, (const double*)prob(a.Hn[par], p),
-                         b.io + wsz * Bc + hsz * p, c->k, (long long)c->n, (long long)c->nA);
+      launch_get_factor(c, /*h=*/false, prob(a.Wn[par], p), b.io + wsz * p);
+      launch_get_factor(c, /*h=*/true, prob(a.Hn[par], p), b.io + wsz * Bc + hsz * p);
       n_iter[p0 + p] = res[(size_t)p * 4];
     }
     HIPCHK(hipGetLastError());
@@ -2422,7 +2358,7 @@ int setup_workspaces(nbmf_ctx* c) {
   HIPCHK(dmalloc(&c->cstartW, sizeof(int) * bW.size()));
   HIPCHK(hipMemcpy(c->cstartH, bH.data(), sizeof(int) * bH.size(), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(c->cstartW, bW.data(), sizeof(int) * bW.size(), hipMemcpyHostToDevice));
-  if (getenv("NBMF_DEBUG"))
+  if (env_set("NBMF_DEBUG"))
     fprintf(stderr, "[nbmf] K_pad=%d path=%d: H-pass %d x %d workgroups (chunk %d blocks, %d slots), W-pass %d x %d (chunk %d, %d slots)\n",
             c->KP, c->data_kind, (int)(c->nA / 64), c->chunksH, c->CH_H, slotsH, (int)(c->mA / 64), c->chunksW, c->CH_W, slotsW);
   for (double** p : {&c->slabH, &c->slabW, &c->lossbuf, &c->lossfin}) {
@@ -2509,23 +2445,31 @@ int set_device(nbmf_ctx* c) {
   return NBMF_OK;
 }
 
-// (also the single-launch engine's end-of-run guard: small_guard)
-int loss_by_launches(nbmf_ctx* c, double* loss) {
+// One sweep over image A and its finalize, the result read back: the loss of the current factors (with_prior: the Beta
+// log-prior sums recomputed first) or their log-likelihood.  collect_timing: fold any recorded sweep events into the
+// totals (nbmf_timing_get).
+int one_shot(nbmf_ctx* c, bool with_prior, int strict, int clip, bool collect_timing, double* out) {
   if (int rc = set_device(c)) return rc;
   if (int rc = ensure_losses(c, 1)) return rc;
   HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int) * 8, c->stream));
-  hipLaunchKernelGGL(prior_kernel, dim3(c->n_prior_blocks), dim3(256), 0, c->stream, c->Hn, c->prior, c->k, c->KP,
-                     (long long)c->n, (long long)c->nA, c->eps);
-  HIPCHK(hipGetLastError());
-  c->prior_src = c->prior;
-  c->n_prior_src = c->n_prior_blocks;
-  if (int rc = enqueue_loglik_pass(c, 0)) return rc;
-  if (int rc = enqueue_finalize(c, 0, 0.0)) return rc;
-  HIPCHK(hipMemcpyAsync(loss, c->losses_d, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (with_prior) {
+    hipLaunchKernelGGL(prior_kernel, dim3(c->n_prior_blocks), dim3(256), 0, c->stream, c->Hn, c->prior, c->k, c->KP,
+                       (long long)c->n, (long long)c->nA, c->eps);
+    HIPCHK(hipGetLastError());
+    c->prior_src = c->prior;
+    c->n_prior_src = c->n_prior_blocks;
+  }
+  if (int rc = enqueue_a_sweep(c, /*with_products=*/false, strict, clip)) return rc;
+  // (a pure log-likelihood has no prior term, and no pad term when strict: -(ll + 0 + 0) / -1 = ll)
+  if (int rc = enqueue_finalize(c, 0, 0.0, /*loglik_only=*/!with_prior, strict)) return rc;
+  HIPCHK(hipMemcpyAsync(out, c->losses_d, sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (c->timing) timing_collect(c);
+  if (collect_timing && c->timing) timing_collect(c);
   return peer_check(c);
 }
+
+// (also the single-launch engine's end-of-run guard: small_guard)
+int loss_by_launches(nbmf_ctx* c, double* loss) { return one_shot(c, /*with_prior=*/true, 0, 0, /*collect_timing=*/true, loss); }
 
 }  // namespace
 
@@ -2689,7 +2633,7 @@ int nbmf_upload_v(nbmf_ctx* c, const void* xv, int x_kind, int64_t ldx, int tran
 
   // cheap host-side guess of the storage path from a sample (the device pack verifies it exactly);
   // NBMF_FORCE_F64=1 keeps binary data on the 8-byte path (measurement only)
-  bool guess_bin = c->storage == NBMF_STORAGE_AUTO && !(getenv("NBMF_FORCE_F64") && atoi(getenv("NBMF_FORCE_F64")) != 0);
+  bool guess_bin = c->storage == NBMF_STORAGE_AUTO && env_int("NBMF_FORCE_F64", 0) == 0;
   bool guess_mask_bin = true;   // a float64 mask holding only 0 and 1 is a binary mask
   {
     const int64_t rows = U < 8 ? U : 8;
@@ -2709,7 +2653,7 @@ int nbmf_upload_v(nbmf_ctx* c, const void* xv, int x_kind, int64_t ldx, int tran
   }
 
   // NBMF_UPLOAD_TRACE=1: where an upload's time goes, stage by stage (host clock, the stream drained at every mark)
-  const bool up_trace = getenv("NBMF_UPLOAD_TRACE") != nullptr;
+  const bool up_trace = env_set("NBMF_UPLOAD_TRACE");
   auto up_t0 = std::chrono::steady_clock::now();
   double up_copy = 0, up_pack = 0;
   auto up_mark = [&](const char* what) {
@@ -2933,8 +2877,7 @@ int nbmf_upload_csr(nbmf_ctx* c, const int64_t* indptr, const int32_t* indices, 
     }
   } d_ptr, d_idx;
   HIPCHK(dmalloc(&d_ptr.p, sizeof(int64_t) * (size_t)(U + 1)));
-  int64_t piece = 64ll << 20;
-  if (const char* e = getenv("NBMF_CSR_PIECE")) piece = std::max<int64_t>(1, atoll(e));   // (tests: force several pieces)
+  const int64_t piece = std::max<int64_t>(1, env_int<int64_t>("NBMF_CSR_PIECE", 64ll << 20));   // (tests: force several pieces)
   HIPCHK(dmalloc(&d_idx.p, sizeof(int32_t) * (size_t)std::max<int64_t>(1, std::min<int64_t>(piece, std::max(nnz, mask_nnz)))));
   for (int what = masked ? 0 : 1; what <= 1; ++what) {
     const int64_t* ip = what == 0 ? mask_indptr : indptr;
@@ -2998,20 +2941,12 @@ int nbmf_set_factors(nbmf_ctx* c, const double* W, const double* H) {
   if (!c || !W || !H) return fail(NBMF_ERR_ARG, "null argument");
   if (int rc = set_device(c)) return rc;
   HIPCHK(hipMemcpyAsync(c->stage, W, sizeof(double) * (size_t)c->k * c->m, hipMemcpyHostToDevice, c->stream));
-  {
-    const long long tot = (long long)c->KP * c->mA;
-    hipLaunchKernelGGL(set_factor_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, c->stage, c->Wn,
-                       c->WT, c->WG, c->k, c->KP, std::min(c->KP, SLICE_K), (long long)c->m, (long long)c->mA);
-    HIPCHK(hipGetLastError());
-  }
+  launch_set_factor(c, /*h=*/false, c->stage, c->Wn, c->WT, c->WG);
+  HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
   HIPCHK(hipMemcpyAsync(c->stage, H, sizeof(double) * (size_t)c->k * c->n, hipMemcpyHostToDevice, c->stream));
-  {
-    const long long tot = (long long)c->KP * c->nA;
-    hipLaunchKernelGGL(set_factor_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, c->stage, c->Hn,
-                       c->HT, c->HG, c->k, c->KP, std::min(c->KP, SLICE_K), (long long)c->n, (long long)c->nA);
-    HIPCHK(hipGetLastError());
-  }
+  launch_set_factor(c, /*h=*/true, c->stage, c->Hn, c->HT, c->HG);
+  HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(prior_kernel, dim3(c->n_prior_blocks), dim3(256), 0, c->stream, c->Hn, c->prior, c->k, c->KP,
                      (long long)c->n, (long long)c->nA, c->eps);
   HIPCHK(hipGetLastError());
@@ -3026,20 +2961,12 @@ int nbmf_get_factors(nbmf_ctx* c, double* W, double* H) {
   if (!c) return fail(NBMF_ERR_ARG, "null context");
   if (!c->have_factors) return fail(NBMF_ERR_STATE, "no factors on the device");
   if (int rc = set_device(c)) return rc;
-  if (W) {
-    const long long tot = (long long)c->k * c->m;
-    hipLaunchKernelGGL(get_factor_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, c->Wn, c->stage,
-                       c->k, (long long)c->m, (long long)c->mA);
+  for (const bool h : {false, true}) {
+    double* out = h ? H : W;
+    if (!out) continue;
+    launch_get_factor(c, h, h ? c->Hn : c->Wn, c->stage);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(W, c->stage, sizeof(double) * (size_t)tot, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-  }
-  if (H) {
-    const long long tot = (long long)c->k * c->n;
-    hipLaunchKernelGGL(get_factor_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, c->Hn, c->stage,
-                       c->k, (long long)c->n, (long long)c->nA);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(H, c->stage, sizeof(double) * (size_t)tot, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out, c->stage, sizeof(double) * (size_t)c->k * (h ? c->n : c->m), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   return NBMF_OK;
@@ -3082,27 +3009,41 @@ int nbmf_run(nbmf_ctx* c, int max_iter, double tol, double* losses, int* n_iter)
   // (config 1, 100x500 K=6: 14.7k it/s replayed vs 16.5k it/s eager) -- tiny problems are bound by the
   // latency of the five dependent kernels, not by the host's launch rate -- so it is opt-in
   // (NBMF_USE_GRAPH=1), never used with a communicator or event timing.
-  const bool use_graph = getenv("NBMF_USE_GRAPH") && !is_sharded(c) && !c->timing && !progress && max_iter >= 8;
+  const bool use_graph = env_set("NBMF_USE_GRAPH") && !is_sharded(c) && !c->timing && !progress && max_iter >= 8;
   bool fused_fin = fin_fusable(c) && !use_graph;
-  // A sweep whose loss assembly ran out of time (PassFin: the chip is shared and this sweep's other workgroups were held
-  // back for seconds) has assembled nothing, raised the stop flag -- every later kernel has returned at once, the factors
-  // are those that sweep read -- and told the host (flags[6]).  `done` losses are in place (flags[1]): the run resumes at
-  // iteration done + 1, whose H sweep is the one that failed, with the loss and stop test in a launch of their own from
-  // here on (bit for bit the fused form's losses: tested).  Slots that filled late are emptied first.
-  auto recover = [&](int done) -> int {
+  int recoveries = 0;
+  int fl[8];
+  // The host's look at the run: the flags read back (the stream drained), the timing, the peer check.  A sweep whose loss
+  // assembly ran out of time (PassFin: the chip is shared and this sweep's other workgroups were held back for seconds) has
+  // assembled nothing, raised the stop flag -- every later kernel has returned at once, the factors are those that sweep
+  // read -- and told the host (flags[6]).  `done` losses are in place (flags[1]): the run resumes (*resume) at iteration
+  // done + 1, whose H sweep is the one that failed, with the loss and stop test in a launch of their own from here on (bit
+  // for bit the fused form's losses: tested).  Slots that filled late are emptied first.  At most 4 recoveries, and at the
+  // end of the run none once it has been cancelled.
+  auto settle = [&](bool at_end, bool* resume) -> int {
+    *resume = false;
+    HIPCHK(hipMemcpyAsync(fl, c->flags, sizeof fl, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->timing) timing_collect(c);
+    if (int rc = peer_check(c)) return rc;
+    if (!fl[6] || !fused_fin || recoveries >= 4 || (at_end && c->cancelled.load(std::memory_order_relaxed))) return NBMF_OK;
+    ++recoveries;
     g_loss_assembly_recoveries.fetch_add(1, std::memory_order_relaxed);
-    if (getenv("NBMF_DEBUG")) fprintf(stderr, "[nbmf] loss %d could not be assembled inside its sweep within the bound: resuming with separate launches\n", done);
+    if (env_set("NBMF_DEBUG")) fprintf(stderr, "[nbmf] loss %d could not be assembled inside its sweep within the bound: resuming with separate launches\n", fl[1]);
     fused_fin = false;
     if (int rc = fill_ll_empty(c)) return rc;
     HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int), c->stream));
     HIPCHK(hipMemsetAsync(c->flags + 6, 0, sizeof(int), c->stream));
+    it = fl[1] + 1;
+    host_done = 0;
+    *resume = true;
     return NBMF_OK;
   };
   hipGraph_t graph = nullptr;
   hipGraphExec_t gexec = nullptr;
   if (use_graph) {
     HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    int rc = enqueue_h_pass(c);
+    int rc = enqueue_a_sweep(c, /*with_products=*/true);
     if (!rc) rc = enqueue_finalize(c, -1, tol);
     if (!rc) rc = enqueue_h_update(c);
     if (!rc) rc = enqueue_w_step(c, c->projection);
@@ -3119,77 +3060,65 @@ int nbmf_run(nbmf_ctx* c, int max_iter, double tol, double* losses, int* n_iter)
       if (g) hipGraphDestroy(g);
     }
   } guard{graph, gexec};
-  for (int recoveries = 0;; ++recoveries) {
-  while (it < max_iter && !host_done) {
-    const int end = std::min(max_iter, it + batch);
-    for (; it < end; ++it) {
-      if (c->cancelled.load(std::memory_order_relaxed)) return fail(NBMF_ERR_STATE, "cancelled (nbmf_cancel)");
-      c->timing_it = it;
-      if (use_graph) {
-        HIPCHK(hipGraphLaunch(gexec, c->stream));
-        continue;
+  for (;;) {
+    if (it < max_iter && !host_done) {
+      // the next batch of iterations; behind it (stop rule, progress reports) a look at the flags
+      const int end = std::min(max_iter, it + batch);
+      for (; it < end; ++it) {
+        if (c->cancelled.load(std::memory_order_relaxed)) return fail(NBMF_ERR_STATE, "cancelled (nbmf_cancel)");
+        c->timing_it = it;
+        if (use_graph) {
+          HIPCHK(hipGraphLaunch(gexec, c->stream));
+          continue;
+        }
+        if (is_sharded(c) && c->shard_axis == 0) {
+          if (int rc = enqueue_iteration_rows(c, it, tol)) return rc;
+          continue;
+        }
+        if (fused_fin) {
+          if (int rc = enqueue_a_sweep(c, true, 0, 0, it - 1, tol)) return rc;   // (with the loss and stop test of iteration it-1)
+        } else {
+          if (int rc = enqueue_a_sweep(c, /*with_products=*/true)) return rc;
+          if (it > 0)
+            if (int rc = enqueue_finalize(c, it - 1, tol)) return rc;
+        }
+        if (int rc = enqueue_h_update(c)) return rc;
+        if (int rc = enqueue_w_step(c, c->projection)) return rc;
       }
-      if (is_sharded(c) && c->shard_axis == 0) {
-        if (int rc = enqueue_iteration_rows(c, it, tol)) return rc;
-        continue;
+      if ((tol > 0.0 || progress) && it < max_iter) {
+        bool resume = false;
+        if (int rc = settle(/*at_end=*/false, &resume)) return rc;
+        if (!resume) {
+          host_done = fl[0];
+          if (int rc = report(fl[1])) return rc;
+        }
       }
+      continue;
+    }
+    if (!host_done) {
+      // loss of the last iteration (Theta-only sweep)
       if (fused_fin) {
-        if (int rc = enqueue_h_pass(c, it - 1, tol)) return rc;   // (with the loss and stop test of iteration it-1)
+        if (int rc = enqueue_a_sweep(c, false, 0, 0, max_iter - 1, tol)) return rc;
       } else {
-        if (int rc = enqueue_h_pass(c)) return rc;
-        if (it > 0)
-          if (int rc = enqueue_finalize(c, it - 1, tol)) return rc;
+        if (int rc = enqueue_a_sweep(c, /*with_products=*/false)) return rc;
+        if (int rc = enqueue_finalize(c, use_graph ? -1 : max_iter - 1, tol)) return rc;
       }
-      if (int rc = enqueue_h_update(c)) return rc;
-      if (int rc = enqueue_w_step(c, c->projection)) return rc;
     }
-    if ((tol > 0.0 || progress) && it < max_iter) {
-      int fl[8];
-      HIPCHK(hipMemcpyAsync(fl, c->flags, sizeof fl, hipMemcpyDeviceToHost, c->stream));
+    bool resume = false;
+    if (int rc = settle(/*at_end=*/true, &resume)) return rc;
+    if (resume) continue;   // the iterations from the one whose sweep failed on (or, behind the last one, only the last loss)
+    if (fl[6]) {   // the loss assembly inside a sweep gave up waiting for a partial (PassFin), and may not be retried
+      if (int rc = fill_ll_empty(c)) return rc;
       HIPCHK(hipStreamSynchronize(c->stream));
-      if (c->timing) timing_collect(c);
-      if (int rc = peer_check(c)) return rc;
-      if (fl[6] && fused_fin && recoveries < 4) {
-        if (int rc = recover(fl[1])) return rc;
-        it = fl[1] + 1;
-        continue;
-      }
-      host_done = fl[0];
-      if (int rc = report(fl[1])) return rc;
+      return fail(NBMF_ERR_STATE, "internal: a sweep's loss assembly timed out waiting for its workgroups' partials");
     }
-  }
-  if (!host_done) {
-    // loss of the last iteration (Theta-only sweep)
-    if (fused_fin) {
-      if (int rc = enqueue_loglik_pass(c, 0, 0, max_iter - 1, tol)) return rc;
-    } else {
-      if (int rc = enqueue_loglik_pass(c, 0)) return rc;
-      if (int rc = enqueue_finalize(c, use_graph ? -1 : max_iter - 1, tol)) return rc;
-    }
-  }
-  int fl[8];
-  HIPCHK(hipMemcpyAsync(fl, c->flags, sizeof fl, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (c->timing) timing_collect(c);
-  if (int rc = peer_check(c)) return rc;
-  if (fl[6]) {   // the loss assembly inside a sweep gave up waiting for a partial (PassFin)
-    if (fused_fin && recoveries < 4 && !c->cancelled.load(std::memory_order_relaxed)) {
-      if (int rc = recover(fl[1])) return rc;
-      it = fl[1] + 1;
-      host_done = 0;
-      continue;   // the iterations from the one whose sweep failed on (or, behind the last one, only the last loss)
-    }
-    if (int rc = fill_ll_empty(c)) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return fail(NBMF_ERR_STATE, "internal: a sweep's loss assembly timed out waiting for its workgroups' partials");
-  }
-  if (c->cancelled.load(std::memory_order_relaxed)) return fail(NBMF_ERR_STATE, "cancelled (nbmf_cancel)");
-  const int nit = fl[1];
-  if (nit < 1 || nit > max_iter) return fail(NBMF_ERR_STATE, "internal: device reported n_iter=%d", nit);
-  if (int rc = report(nit)) return rc;
-  HIPCHK(hipMemcpy(losses, c->losses_d, sizeof(double) * (size_t)nit, hipMemcpyDeviceToHost));
-  *n_iter = nit;
-  return NBMF_OK;
+    if (c->cancelled.load(std::memory_order_relaxed)) return fail(NBMF_ERR_STATE, "cancelled (nbmf_cancel)");
+    const int nit = fl[1];
+    if (nit < 1 || nit > max_iter) return fail(NBMF_ERR_STATE, "internal: device reported n_iter=%d", nit);
+    if (int rc = report(nit)) return rc;
+    HIPCHK(hipMemcpy(losses, c->losses_d, sizeof(double) * (size_t)nit, hipMemcpyDeviceToHost));
+    *n_iter = nit;
+    return NBMF_OK;
   }
 }
 
@@ -3280,28 +3209,13 @@ int nbmf_loss(nbmf_ctx* c, double* loss) {
 int nbmf_loglik(nbmf_ctx* c, int clip_theta, double* loglik) {
   if (int rc = ready(c)) return rc;
   if (!loglik) return fail(NBMF_ERR_ARG, "null output");
-  if (int rc = set_device(c)) return rc;
-  if (int rc = ensure_losses(c, 1)) return rc;
-  HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int) * 8, c->stream));
-  if (int rc = enqueue_loglik_pass(c, 0, clip_theta != 0)) return rc;
-  if (int rc = enqueue_finalize(c, 0, 0.0, /*loglik_only=*/true)) return rc;   // -(ll + 0 + 0) / -1 = ll
-  HIPCHK(hipMemcpyAsync(loglik, c->losses_d, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (c->timing) timing_collect(c);
-  return peer_check(c);
+  return one_shot(c, /*with_prior=*/false, /*strict=*/0, clip_theta != 0, /*collect_timing=*/true, loglik);
 }
 
 int nbmf_loglik_strict(nbmf_ctx* c, double* loglik) {
   if (int rc = ready(c)) return rc;
   if (!loglik) return fail(NBMF_ERR_ARG, "null output");
-  if (int rc = set_device(c)) return rc;
-  if (int rc = ensure_losses(c, 1)) return rc;
-  HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int) * 8, c->stream));
-  if (int rc = enqueue_loglik_pass(c, 1)) return rc;
-  if (int rc = enqueue_finalize(c, 0, 0.0, /*loglik_only=*/true, /*strict=*/1)) return rc;   // no pad term, no prior
-  HIPCHK(hipMemcpyAsync(loglik, c->losses_d, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return peer_check(c);
+  return one_shot(c, /*with_prior=*/false, /*strict=*/1, /*clip=*/0, /*collect_timing=*/false, loglik);
 }
 
 int nbmf_comm_unique_id(void* id128) {
@@ -3322,8 +3236,7 @@ static int comm_finish_init(nbmf_ctx* c, int nranks, int rank, int shard_axis) {
   // hide half of the exchange but cost ~35 us per iteration in extra launches and a split W-pass (measured
   // with one rank, where there is nothing to hide); the break-even is an all-reduce of ~70 us, which cannot
   // be timed on a one-GPU box, so the default stays one panel.
-  const char* ov = getenv("NBMF_OVERLAP");
-  const bool two = c->panels_wanted ? c->panels_wanted == 2 : (ov && atoi(ov) != 0);
+  const bool two = c->panels_wanted ? c->panels_wanted == 2 : env_int("NBMF_OVERLAP", 0) != 0;
   c->npanel = (shard_axis == 0 && c->KS == 1 && c->chunksW >= 2 && two) ? 2 : 1;
   c->wsplit = c->npanel == 2 ? c->chunksW / 2 : c->chunksW;
   c->pc0[0] = 0;
@@ -3332,7 +3245,7 @@ static int comm_finish_init(nbmf_ctx* c, int nranks, int rank, int shard_axis) {
   c->pbase[0] = 0;
   c->ll_index = 2 * (size_t)c->KP * c->pc0[1];
   c->pbase[1] = c->ll_index + 2;
-  if (getenv("NBMF_DEBUG"))
+  if (env_set("NBMF_DEBUG"))
     fprintf(stderr, "[nbmf] rank %d/%d axis %d: %d exchange panel(s), columns split at %lld of %lld, W-pass chunks %d + %d, %s\n",
             rank, nranks, shard_axis, c->npanel, c->pc0[1], (long long)c->nA, c->wsplit, c->chunksW - c->wsplit,
             c->comm ? "RCCL" : c->peer ? "peer (xGMI)" : "host transport");
@@ -3540,8 +3453,7 @@ int nbmf_comm_init_peer(nbmf_ctx* c, const void* handles, int nranks, int rank, 
   PeerView pv{};
   pv.nranks = nranks;
   pv.rank = rank;
-  double ms = 30000.0;
-  if (const char* e = getenv("NBMF_PEER_TIMEOUT_MS")) ms = std::max(1.0, atof(e));
+  double ms = std::max(1.0, env_double("NBMF_PEER_TIMEOUT_MS", 30000.0));
   if (c->peer_timeout_ms > 0) ms = c->peer_timeout_ms;
   pv.timeout = (unsigned long long)(ms * 1e5);   // wall_clock64 ticks at 100 MHz
   struct Undo {   // any failure below leaves the context unattached
