@@ -212,6 +212,27 @@ int nbmf_loglik(nbmf_ctx* ctx, int clip_theta, double* loglik);
  * nbmf_get_n_obs, negate, exponentiate).  A Theta-only sweep (no back-products). */
 int nbmf_loglik_strict(nbmf_ctx* ctx, double* loglik);
 
+/* Theta at `count` index pairs of the internal m x n matrix, for the factors the context holds
+ * (after nbmf_set_factors or a run): out[t] = Theta[rows[t], cols[t]], clipped to [0, 1] first if
+ * clip_theta != 0 (NBMFMM.inverse_transform, _base.py:201-210).  Needs factors, not data; NBMF_ERR_STATE while a
+ * communicator is attached (detach first).  Every pair is checked on the device before it is used: one outside
+ * [0, m) x [0, n) gives NBMF_ERR_ARG with the lowest offending position in the message (what `out` holds is unspecified
+ * then), and the context stays usable.  Runs in chunks of NBMF_PREDICT_PAIRS pairs (environment; default 1 << 22); the value
+ * at a pair depends on the pair and the factors only.  Synchronises the context's stream before it returns. */
+int nbmf_predict_at(nbmf_ctx* ctx, const int64_t* rows, const int64_t* cols, int64_t count,
+                    int clip_theta, double* out);
+
+/* Theta for rows [row0, row0 + nrows) and all n columns.
+ * NBMF_PREDICT_F64: float64, `out` row-major with leading dimension ldout (elements, >= n).
+ * NBMF_PREDICT_U8:  one byte per entry, 1 where theta > threshold (strictly; theta after the clip
+ *                   if clip_theta), else 0; ldout in bytes.  Columns n .. ldout-1 of `out` are not written.
+ * Runs in panels of NBMF_PREDICT_PANEL_ROWS rows (environment; default: the multiple of 16 that keeps a panel at or under
+ * 256 MiB); an entry's value does not depend on the panels.  Same state rules and synchronisation as above. */
+#define NBMF_PREDICT_F64 0
+#define NBMF_PREDICT_U8 1
+int nbmf_predict_rows(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int clip_theta, int out_kind,
+                      double threshold, void* out, int64_t ldout);
+
 /* Multi-GPU, one process (and one context) per GPU.  The internal matrix Y is split over the ranks along
  *   shard_axis 0: its ROWS    -> W[:, rows] is local, H is replicated; each iteration all-reduces the k x n
  *                 H-step products [P1 | P2 | loglik] (2*K*N+1 doubles) before the H-update;

@@ -8,7 +8,8 @@ import numpy as np
 from sklearn.base import BaseEstimator, TransformerMixin
 from sklearn.utils import check_array
 
-from ._solver import device_score, nbmf_mm_restarts, nbmf_mm_solver, w_only_transform
+from . import _hip
+from ._solver import device_predict, device_score, nbmf_mm_restarts, nbmf_mm_solver, w_only_transform
 from ._utils import check_is_fitted
 
 # Accepted spellings of the two orientations: the exact strings of src/nbmf_mm/_base.py:127-137
@@ -187,10 +188,66 @@ class NBMFMM(BaseEstimator, TransformerMixin):
             self._finite_or_binary_error(X, e)
 
     def inverse_transform(self, W):
-        """clip(W @ components_, 0, 1) (_base.py:201-210)."""
+        """clip(W @ components_, 0, 1) (_base.py:201-210), on the host; :meth:`predict_proba` is the same on the device,
+        whole or at chosen entries."""
         check_is_fitted(self, ["components_"])
         W = check_array(W, dtype=np.float64)
         return np.clip(W @ self.components_, 0.0, 1.0)
+
+    # -- prediction on the device (no reference counterpart beyond inverse_transform) ----------------------------
+    def _prediction_factors(self, W):
+        check_is_fitted(self, ["components_"])
+        H = np.asarray(self.components_, dtype=np.float64)
+        if W is None:
+            check_is_fitted(self, ["W_"])
+            W = self.W_
+        W = check_array(W, dtype=np.float64)
+        if W.shape[1] != H.shape[0]:
+            raise ValueError(f"W has {W.shape[1]} columns, the model has {H.shape[0]} components")
+        return W, H
+
+    def predict_proba(self, W=None, rows=None, cols=None):
+        """Theta = clip(W @ components_, 0, 1) computed on the GPU, ``W`` defaulting to ``W_``: the dense
+        ``(W.shape[0], n_features)`` float64 matrix (``inverse_transform(W)`` to rounding), or, with the integer arrays
+        ``rows`` and ``cols``, the 1-D array of ``Theta[rows[t], cols[t]]`` -- only those entries are formed.
+        Measured on an MI355X at 65536 x 8192, K = 64 (profiles/predict_on_device.txt): 2^22 pairs in
+        4.7 ms against 0.95 s for ``inverse_transform(W)[rows, cols]``; a dense 8192-row slab in 10.1 ms against 116 ms,
+        nearly all of it the copy of the result to the host."""
+        W, H = self._prediction_factors(W)
+        if (rows is None) != (cols is None):
+            raise ValueError("rows and cols go together: give both or neither")
+        if rows is not None:
+            rows, cols = _hip.index_pairs(rows, cols)
+        return device_predict(W, H, rows=rows, cols=cols, device=self.device)
+
+    def predict(self, W=None, threshold=0.5):
+        """The bool matrix ``predict_proba(W) > threshold``, compared on the device: one byte per entry comes back."""
+        W, H = self._prediction_factors(W)
+        threshold = float(threshold)
+        if np.isnan(threshold):
+            raise ValueError("threshold is NaN")
+        return device_predict(W, H, threshold=threshold, device=self.device)
+
+    def impute(self, X, mask):
+        """A float64 copy of ``X`` in which every entry with ``mask == 0`` is replaced by ``predict_proba`` at exactly
+        that position (``W_``, so ``X`` is the fitted matrix or one of its shape); observed entries are returned as given."""
+        check_is_fitted(self, ["components_", "W_"])
+        if mask is None:
+            raise ValueError("impute needs the mask that marks the observed entries")
+        X = self._validated(X)
+        want = (np.shape(self.W_)[0], np.shape(self.components_)[1])
+        if X.shape != want:
+            raise ValueError(f"X has shape {X.shape}, the fitted model describes {want}")
+        if hasattr(mask, "toarray"):
+            mask = mask.toarray()
+        mask = np.asarray(mask)
+        if mask.shape != X.shape:
+            mask = np.broadcast_to(mask, X.shape)              # as fit's Y * mask does
+        out = np.array(X, dtype=np.float64)
+        rows, cols = np.nonzero(mask == 0)
+        if rows.size:
+            out[rows, cols] = self.predict_proba(rows=rows, cols=cols)
+        return out
 
     def score(self, X, mask=None):
         """Mean log-likelihood per observed entry of the reconstruction (_base.py:212-247).

@@ -37,8 +37,10 @@ SYMBOLS = [
     "nbmf_set_progress", "nbmf_device_synchronize", "nbmf_small_stats", "nbmf_generate_slice", "nbmf_set_storage",
     "nbmf_set_exchange_panels", "nbmf_set_peer_timeout_ms", "nbmf_run_batch", "nbmf_batch_stats", "nbmf_sweep_info",
     "nbmf_upload_v", "nbmf_selftest_mfma_peak", "nbmf_engine_stats", "nbmf_source_hash", "nbmf_comm_info", "nbmf_cancel", "nbmf_variant_stats", "nbmf_device_bus_id",
+    "nbmf_predict_at", "nbmf_predict_rows",
 ]
 DATA_F64, DATA_U8, DATA_F32 = 0, 1, 2
+PREDICT_F64, PREDICT_U8 = 0, 1
 
 
 #: int fn(void* user, double* buf, int64 count) -- in-place sum over ranks on a host buffer
@@ -170,6 +172,8 @@ def load():
     lib.nbmf_device_synchronize.argtypes = [c_int]
     lib.nbmf_small_stats.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int)]
     lib.nbmf_selftest_unary.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p]
+    lib.nbmf_predict_at.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]
+    lib.nbmf_predict_rows.argtypes = [c_void_p, c_int64, c_int64, c_int, c_int, c_double, c_void_p, c_int64]
     for name in SYMBOLS:
         if name not in ("nbmf_last_error", "nbmf_source_hash"):
             getattr(lib, name).restype = c_int
@@ -228,6 +232,20 @@ def device_bus_id(device=0) -> str:
 
 def _f64c(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def index_pairs(rows, cols):
+    """The two index arrays of ``predict_at`` as the library takes them (C-contiguous int64), after the checks that need
+    no device: integer-typed, 1-D, equally long.  Raises ``ValueError`` otherwise."""
+    rows, cols = np.asarray(rows), np.asarray(cols)
+    for name, a in (("rows", rows), ("cols", cols)):
+        if not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"{name} must be an integer array (got dtype {a.dtype})")
+        if a.ndim != 1:
+            raise ValueError(f"{name} must be 1-D (got shape {a.shape})")
+    if rows.shape != cols.shape:
+        raise ValueError(f"rows and cols must be equally long (got {rows.size} and {cols.size})")
+    return np.ascontiguousarray(rows, dtype=np.int64), np.ascontiguousarray(cols, dtype=np.int64)
 
 
 class Context:
@@ -403,6 +421,39 @@ class Context:
         v = c_double(0)
         _check(self._lib.nbmf_loglik_strict(self._h, byref(v)))
         return v.value
+
+    def predict_at(self, rows, cols, clip_theta=True):
+        """Theta = W^T H of the current factors at the index pairs ``(rows[t], cols[t])`` of the internal m x n matrix
+        (``nbmf_predict_at``): a float64 1-D array.  Needs factors, not data.  An index outside the matrix raises
+        ``ValueError`` naming the lowest offending position; the context stays usable."""
+        rows, cols = index_pairs(rows, cols)
+        out = np.empty(rows.size, dtype=np.float64)
+        _check(self._lib.nbmf_predict_at(self._h, rows.ctypes.data_as(c_void_p), cols.ctypes.data_as(c_void_p), int(rows.size),
+                                         int(bool(clip_theta)), out.ctypes.data_as(c_void_p)))
+        return out
+
+    def predict_rows(self, row0=0, nrows=None, clip_theta=True, threshold=None, out=None):
+        """Theta for rows ``[row0, row0 + nrows)`` and all n columns (``nbmf_predict_rows``): a float64 ``(nrows, n)``
+        array, or with a ``threshold`` the bool array ``Theta > threshold``, compared on the device (one byte per entry
+        comes back).  ``out``, if given, is written and returned: shape ``(nrows, n)``, float64 (bool or uint8 with a
+        threshold), unit stride along a row and any row stride of at least n elements -- a slice of a wider array is fine,
+        and nothing outside the slice is touched."""
+        row0 = int(row0)
+        nrows = self.m - row0 if nrows is None else int(nrows)
+        byte_kind = threshold is not None
+        if out is None:
+            out = np.empty((max(nrows, 0), self.n), dtype=np.bool_ if byte_kind else np.float64)
+        else:
+            ok_types = (np.bool_, np.uint8) if byte_kind else (np.float64,)
+            if not isinstance(out, np.ndarray) or out.dtype not in ok_types or out.shape != (nrows, self.n):
+                raise ValueError(f"out must be a {ok_types[0].__name__} array of shape ({nrows}, {self.n})")
+            if out.size and (out.strides[1] != out.itemsize or (nrows > 1 and (
+                    out.strides[0] < self.n * out.itemsize or out.strides[0] % out.itemsize))):
+                raise ValueError("out must have unit stride along a row and a row stride of at least n elements")
+        ld = out.strides[0] // out.itemsize if out.size and out.shape[0] > 1 else self.n
+        _check(self._lib.nbmf_predict_rows(self._h, row0, nrows, int(bool(clip_theta)), PREDICT_U8 if byte_kind else PREDICT_F64,
+                                           float(threshold) if byte_kind else 0.0, out.ctypes.data_as(c_void_p), int(ld)))
+        return out
 
     def comm_init(self, uid: bytes, nranks: int, rank: int, shard_axis: int = 0):
         """Attach an RCCL communicator; shard_axis 0 = rows of the internal Y are split, 1 = columns."""

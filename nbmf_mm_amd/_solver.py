@@ -251,3 +251,18 @@ def device_score(X, H, mask=None, n_iter=50, device=0):
         ll = ctx.loglik(clip_theta=True)
         n_obs = ctx.n_obs()
     return float(ll / n_obs)
+
+
+def device_predict(W, H, rows=None, cols=None, threshold=None, device=0):
+    """Theta = ``W @ H`` clipped to [0, 1] (``NBMFMM.inverse_transform``, src/nbmf_mm/_base.py:201-210) on the GPU, for
+    ``W`` (rows, k) and ``H`` (k, features) as the estimator holds them (user layout in both orientations: the solver
+    has un-transposed them).  With ``rows`` / ``cols`` (already validated: ``_hip.index_pairs``) the values at those
+    pairs; otherwise the dense matrix, as float64 or, with a ``threshold``, as the bool matrix ``Theta > threshold``
+    compared on the device.  The context holds factors only: no data is uploaded."""
+    m, k = W.shape
+    n = H.shape[1]
+    with _hip.Context(m, n, k, device=device) as ctx:
+        ctx.set_factors(np.ascontiguousarray(W.T), H)
+        if rows is not None:
+            return ctx.predict_at(rows, cols, clip_theta=True)
+        return ctx.predict_rows(0, m, clip_theta=True, threshold=threshold)

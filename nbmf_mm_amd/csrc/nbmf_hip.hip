@@ -319,6 +319,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 #include "nbmf_pack_kernels.inc"
 #include "nbmf_peer_kernels.inc"
 #include "nbmf_small_kernel.inc"
+#include "nbmf_predict_kernels.inc"
 
 }  // namespace
 
@@ -2475,6 +2476,32 @@ int one_shot(nbmf_ctx* c, bool with_prior, int strict, int clip, bool collect_ti
 // (also the single-launch engine's end-of-run guard: small_guard)
 int loss_by_launches(nbmf_ctx* c, double* loss) { return one_shot(c, /*with_prior=*/true, 0, 0, /*collect_timing=*/true, loss); }
 
+// Staging of one predict call (nbmf_predict_at / nbmf_predict_rows), from the pool: given back when the call returns, on
+// every path, after the stream has drained (a pooled block may be handed to the next caller at once).
+struct PredictStage {
+  hipStream_t stream;
+  std::vector<void*> blocks;
+  template <typename T>
+  hipError_t get(T** out, size_t bytes) {
+    hipError_t e = dmalloc(out, bytes);
+    if (e == hipSuccess) blocks.push_back((void*)*out);
+    return e;
+  }
+  ~PredictStage() {
+    if (blocks.empty()) return;
+    (void)hipStreamSynchronize(stream);
+    for (void* p : blocks) dfree(p);
+  }
+};
+
+// The checks both predict entry points share, in the order the header gives them: factors, not data (so not ready()).
+int predict_ready(nbmf_ctx* c) {
+  if (!c) return fail(NBMF_ERR_ARG, "null context");
+  if (!c->have_factors) return fail(NBMF_ERR_STATE, "no factors on the device");
+  if (is_sharded(c)) return fail(NBMF_ERR_STATE, "prediction runs on an unsharded context (nbmf_comm_detach first)");
+  return NBMF_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -2482,7 +2509,7 @@ int loss_by_launches(nbmf_ctx* c, double* loss) { return one_shot(c, /*with_prio
 // ------------------------------------------------------------------------------------------
 extern "C" {
 
-int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id
+int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows: a compatible addition, which a caller detects by the symbol
 // The sources this binary was compiled from: first 12 hex digits of the SHA-256 over nbmf_hip.hip, the *.inc files (sorted
 // by name) and include/nbmf_hip.h, put in by the Makefile (tools/src_hash.sh prints the same for the tree).  A profile or a
 // bench line that quotes it can be tied to a commit; a library built by hand without the Makefile says "unstamped".
@@ -3220,6 +3247,94 @@ int nbmf_loglik_strict(nbmf_ctx* c, double* loglik) {
   if (int rc = ready(c)) return rc;
   if (!loglik) return fail(NBMF_ERR_ARG, "null output");
   return one_shot(c, /*with_prior=*/false, /*strict=*/1, /*clip=*/0, /*collect_timing=*/false, loglik);
+}
+
+// ---- Theta handed back: index pairs and row slabs (nbmf_predict_kernels.inc) ----------------------------
+int nbmf_predict_at(nbmf_ctx* c, const int64_t* rows, const int64_t* cols, int64_t count, int clip_theta, double* out) {
+  if (int rc = predict_ready(c)) return rc;
+  if (count < 0) return fail(NBMF_ERR_ARG, "count must be >= 0 (got %lld)", (long long)count);
+  if (count == 0) return NBMF_OK;
+  if (!rows || !cols || !out) return fail(NBMF_ERR_ARG, "null argument");
+  if (int rc = set_device(c)) return rc;
+  const long long chunk = std::min<long long>(count, std::max<long long>(1, env_int("NBMF_PREDICT_PAIRS", 1LL << 22)));
+  const size_t K = (size_t)c->k;
+  PredictStage st{c->stream, {}};
+  double *Wk = nullptr, *Hk = nullptr, *out_d = nullptr;
+  long long *rows_d = nullptr, *cols_d = nullptr;
+  unsigned long long* bad_d = nullptr;
+  HIPCHK(st.get(&Wk, sizeof(double) * K * (size_t)c->m));
+  HIPCHK(st.get(&Hk, sizeof(double) * K * (size_t)c->n));
+  HIPCHK(st.get(&rows_d, sizeof(long long) * (size_t)chunk));
+  HIPCHK(st.get(&cols_d, sizeof(long long) * (size_t)chunk));
+  HIPCHK(st.get(&out_d, sizeof(double) * (size_t)chunk));
+  HIPCHK(st.get(&bad_d, sizeof(unsigned long long)));
+  for (const bool h : {false, true}) {   // the k-major copies of the two factors, once per call
+    const long long len = h ? c->n : c->m, lenA = h ? c->nA : c->mA;
+    hipLaunchKernelGGL(k_major_kernel, dim3((unsigned)((len + PT_TILE - 1) / PT_TILE), (unsigned)((c->k + PT_TILE - 1) / PT_TILE)),
+                       dim3(PT_TILE * 8), 0, c->stream, (const double*)(h ? c->Hn : c->Wn), h ? Hk : Wk, c->k, len, lenA);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipMemsetAsync(bad_d, 0xff, sizeof(unsigned long long), c->stream));
+  for (long long base = 0; base < count; base += chunk) {
+    const long long cnt = std::min(chunk, (long long)count - base);
+    HIPCHK(hipMemcpyAsync(rows_d, rows + base, sizeof(long long) * (size_t)cnt, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(cols_d, cols + base, sizeof(long long) * (size_t)cnt, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(predict_at_kernel, dim3((unsigned)((cnt * PA_LANES + 255) / 256)), dim3(256), 0, c->stream, (const double*)Wk,
+                       (const double*)Hk, c->k, (long long)c->m, (long long)c->n, (const long long*)rows_d, (const long long*)cols_d, cnt,
+                       base, clip_theta != 0 ? 1 : 0, bad_d, out_d);
+    HIPCHK(hipGetLastError());
+    unsigned long long bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, bad_d, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (bad != ~0ull)   // (chunks run in ascending order: the first chunk that reports holds the lowest position of all)
+      return fail(NBMF_ERR_ARG, "index pair at position %llu is outside [0, %lld) x [0, %lld)", bad, (long long)c->m,
+                  (long long)c->n);
+    HIPCHK(hipMemcpyAsync(out + base, out_d, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return NBMF_OK;
+}
+
+int nbmf_predict_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, int out_kind, double threshold, void* out,
+                      int64_t ldout) {
+  if (int rc = predict_ready(c)) return rc;
+  if (nrows < 0 || row0 < 0 || row0 > c->m || nrows > c->m - row0)
+    return fail(NBMF_ERR_ARG, "rows [%lld, %lld + %lld) are not inside [0, %lld)", (long long)row0, (long long)row0, (long long)nrows,
+                (long long)c->m);
+  if (ldout < c->n) return fail(NBMF_ERR_ARG, "ldout %lld is less than n = %lld", (long long)ldout, (long long)c->n);
+  if (out_kind != NBMF_PREDICT_F64 && out_kind != NBMF_PREDICT_U8) return fail(NBMF_ERR_ARG, "unknown out_kind %d", out_kind);
+  if (out_kind == NBMF_PREDICT_U8 && threshold != threshold) return fail(NBMF_ERR_ARG, "threshold is NaN");
+  if (nrows == 0) return NBMF_OK;
+  if (!out) return fail(NBMF_ERR_ARG, "null output");
+  if (int rc = set_device(c)) return rc;
+  const size_t elt = out_kind == NBMF_PREDICT_U8 ? 1 : sizeof(double);
+  const long long ldd = round_up(c->n, 4);   // (<= nA) the panel's leading dimension: the kernel stores 4 entries at a time
+  const long long dflt = std::max<long long>(16, (long long)((256ull << 20) / ((size_t)ldd * elt)) / 16 * 16);
+  const long long panel = std::min<long long>(nrows, std::max<long long>(1, env_int("NBMF_PREDICT_PANEL_ROWS", dflt)));
+  const long long col_groups = (c->nA + PR_WAVES * PR_STRIP - 1) / (PR_WAVES * PR_STRIP);
+  if (col_groups > 65535) return fail(NBMF_ERR_ARG, "n = %lld is beyond what nbmf_predict_rows launches", (long long)c->n);
+  PredictStage st{c->stream, {}};
+  char* panel_d = nullptr;
+  HIPCHK(st.get(&panel_d, (size_t)panel * ldd * elt));
+  for (long long p0 = row0; p0 < row0 + nrows; p0 += panel) {
+    const long long pn = std::min(panel, (long long)(row0 + nrows) - p0);
+    const dim3 grid((unsigned)((p0 + pn + 15) / 16 - p0 / 16), (unsigned)col_groups);
+    if (out_kind == NBMF_PREDICT_U8)
+      hipLaunchKernelGGL(predict_rows_kernel<1>, grid, dim3(PR_WAVES * 64), 0, c->stream, (const double*)c->Wn, (const double*)c->Hn,
+                         c->k, (long long)c->mA, (long long)c->nA, p0, pn, ldd, clip_theta != 0 ? 1 : 0, threshold, (void*)panel_d);
+    else
+      hipLaunchKernelGGL(predict_rows_kernel<0>, grid, dim3(PR_WAVES * 64), 0, c->stream, (const double*)c->Wn, (const double*)c->Hn,
+                         c->k, (long long)c->mA, (long long)c->nA, p0, pn, ldd, clip_theta != 0 ? 1 : 0, threshold, (void*)panel_d);
+    HIPCHK(hipGetLastError());
+    char* dst = (char*)out + (size_t)(p0 - row0) * (size_t)ldout * elt;
+    if (ldout == c->n && ldd == c->n)   // (nothing of `out` beyond column n - 1 is ever written)
+      HIPCHK(hipMemcpyAsync(dst, panel_d, (size_t)pn * ldd * elt, hipMemcpyDeviceToHost, c->stream));
+    else
+      HIPCHK(hipMemcpy2DAsync(dst, (size_t)ldout * elt, panel_d, (size_t)ldd * elt, (size_t)c->n * elt, (size_t)pn,
+                              hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
+  }
+  return NBMF_OK;
 }
 
 int nbmf_comm_unique_id(void* id128) {

@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""Prediction on the device against the host routes it replaces, at the headline shape (65536 x 8192, K = 64): seeded
+random factors, no data upload.  One command, one machine, every leg warmed once, median of five, wall time around calls
+that end in a synchronise (the library's predict calls do; NumPy's are synchronous).
+
+  (a) Theta at 2^22 seeded random index pairs: Context.predict_at against the cheapest host route (a gathered einsum over
+      W[rows] and H[:, cols]) and against the only route the estimator had before (inverse_transform(W)[rows, cols]: the
+      whole 69 GFLOP product and its 4.3 GB array);
+  (b) Theta for 8192 rows, as float64 and as bytes (> 0.5): Context.predict_rows against np.clip(W[:8192] @ H, 0, 1).
+
+The host legs are the comparison; the device path is never its own yardstick.  Before any time is taken the device and host
+results are compared at these sizes within tests/test_gpu_predict.py's bound, 2.1 K 2^-53 (|W| @ |H|) per entry.
+Prints progress lines and, last, ONE JSON line.  Needs an MI355X: there is no CPU fallback."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+from nbmf_mm_amd import _hip  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--m", type=int, default=65536)
+ap.add_argument("--n", type=int, default=8192)
+ap.add_argument("--k", type=int, default=64)
+ap.add_argument("--pairs", type=int, default=1 << 22)
+ap.add_argument("--rows", type=int, default=8192)
+ap.add_argument("--reps", type=int, default=5)
+args = ap.parse_args()
+m, n, k, P, R = args.m, args.n, args.k, args.pairs, min(args.rows, args.m)
+
+
+def median_s(fn):
+    fn()                                                    # warm-up: code objects, pools, page faults of the outputs
+    ts = []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts)), [round(t, 6) for t in ts]
+
+
+def say(*a):
+    print(*a, flush=True)
+
+
+g = np.random.default_rng(2024)
+W = g.uniform(0.1, 0.9, (m, k))
+W /= W.sum(1, keepdims=True)                                # user layout: W (m, k) rows on the simplex, H (k, n) in (0, 1)
+H = g.uniform(0.05, 0.95, (k, n))
+rows, cols = g.integers(0, m, P), g.integers(0, n, P)
+unit = 2.1 * k * 2.0 ** -53                                 # the bound is unit * (|W| @ |H|); the factors are positive
+
+res = {"tool": "bench_predict", "library": _hip.source_hash(), "shape": [m, n, k], "pairs": P, "slab_rows": R, "reps": args.reps}
+with _hip.Context(m, n, k) as ctx:
+    ctx.set_factors(np.ascontiguousarray(W.T), H)
+
+    # ---- agreement first ----------------------------------------------------------------------------------------------
+    def host_einsum():
+        return np.clip(np.einsum("pk,kp->p", W[rows], H[:, cols]), 0.0, 1.0)
+
+    def host_parent():
+        return np.clip(W @ H, 0.0, 1.0)[rows, cols]         # inverse_transform(W)[rows, cols]
+
+    def host_slab():
+        return np.clip(W[:R] @ H, 0.0, 1.0)
+
+    ref_at = host_einsum()
+    dev_at = ctx.predict_at(rows, cols)
+    worst_at = float(np.max(np.abs(dev_at - ref_at) / (unit * ref_at)))
+    assert worst_at <= 1.0, f"predict_at is {worst_at} bounds away from the host product"
+    ref_slab = host_slab()
+    out64 = np.empty((R, n))
+    out8 = np.empty((R, n), dtype=np.bool_)
+    ctx.predict_rows(0, R, out=out64)
+    worst_rows = float(np.max(np.abs(out64 - ref_slab) / (unit * ref_slab)))
+    assert worst_rows <= 1.0, f"predict_rows is {worst_rows} bounds away from the host product"
+    ctx.predict_rows(0, R, threshold=0.5, out=out8)
+    decided = np.abs(ref_slab - 0.5) > unit * ref_slab      # entries the bound lets either side call
+    assert np.array_equal(out8[decided], ref_slab[decided] > 0.5), "the byte slab disagrees with the host product"
+    res["agreement"] = {"predict_at_worst_over_bound": worst_at, "predict_rows_worst_over_bound": worst_rows,
+                        "byte_entries_within_bound_of_threshold": int(decided.size - decided.sum())}
+    say("agreement:", res["agreement"])
+    del ref_at, dev_at, decided
+
+    # ---- (a) pairs -------------------------------------------------------------------------------------------------------
+    a = {}
+    a["device_s"], a["device_all_s"] = median_s(lambda: ctx.predict_at(rows, cols))
+    say("predict_at", a["device_s"])
+    a["host_einsum_s"], a["host_einsum_all_s"] = median_s(host_einsum)
+    say("host einsum", a["host_einsum_s"])
+    a["host_inverse_transform_s"], a["host_inverse_transform_all_s"] = median_s(host_parent)
+    say("host inverse_transform", a["host_inverse_transform_s"])
+    a["gathered_factor_bytes"] = 2 * k * 8 * P
+    a["device_gathered_GBps"] = a["gathered_factor_bytes"] / a["device_s"] / 1e9
+    a["speedup_vs_einsum"] = a["host_einsum_s"] / a["device_s"]
+    a["speedup_vs_inverse_transform"] = a["host_inverse_transform_s"] / a["device_s"]
+    res["pairs_leg"] = a
+
+    # ---- (b) slabs -------------------------------------------------------------------------------------------------------
+    b = {}
+    b["device_f64_s"], b["device_f64_all_s"] = median_s(lambda: ctx.predict_rows(0, R, out=out64))
+    say("predict_rows f64", b["device_f64_s"])
+    b["device_u8_s"], b["device_u8_all_s"] = median_s(lambda: ctx.predict_rows(0, R, threshold=0.5, out=out8))
+    say("predict_rows u8", b["device_u8_s"])
+    b["host_f64_s"], b["host_f64_all_s"] = median_s(host_slab)
+    say("host slab", b["host_f64_s"])
+    b["host_u8_s"], b["host_u8_all_s"] = median_s(lambda: host_slab() > 0.5)
+    say("host slab > 0.5", b["host_u8_s"])
+    b["f64_output_bytes"], b["u8_output_bytes"] = R * n * 8, R * n
+    b["device_f64_output_GBps"] = b["f64_output_bytes"] / b["device_f64_s"] / 1e9
+    b["device_u8_output_GBps"] = b["u8_output_bytes"] / b["device_u8_s"] / 1e9
+    # The two device legs run the same product and differ in the bytes that cross PCIe (8 against 1 per entry): their
+    # difference is the time of 7/8 of the float64 copy.  An estimate derived from two end-to-end times, not a trace.
+    copy_s = max(0.0, b["device_f64_s"] - b["device_u8_s"]) * 8.0 / 7.0
+    b["f64_pcie_share_estimated"] = min(1.0, copy_s / b["device_f64_s"])
+    b["speedup_f64_vs_host"] = b["host_f64_s"] / b["device_f64_s"]
+    b["speedup_u8_vs_host"] = b["host_u8_s"] / b["device_u8_s"]
+    res["slab_leg"] = b
+
+print(json.dumps(res))
