@@ -233,6 +233,21 @@ int nbmf_predict_at(nbmf_ctx* ctx, const int64_t* rows, const int64_t* cols, int
 int nbmf_predict_rows(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int clip_theta, int out_kind,
                       double threshold, void* out, int64_t ldout);
 
+/* The `top` columns with the largest Theta in each of the rows [row0, row0 + nrows), ranked on the device: for every
+ * row i and slot s < top, out_cols[(i - row0) * ldout + s] is the s-th column in the order "Theta descending (compared
+ * numerically), ties by ascending column" over the ELIGIBLE columns of the row, and out_scores (may be NULL) its Theta.
+ * A column j in [0, n) is eligible unless exclude[(i - row0) * ldx + j] != 0 (exclude may be NULL: nothing is skipped;
+ * otherwise nrows x n bytes, ldx >= n, nothing beyond column n - 1 is read) or Theta[i, j] is NaN.  Theta[i, j] is bit
+ * for bit the entry nbmf_predict_rows(..., clip_theta, NBMF_PREDICT_F64, ...) returns.  A row with fewer than `top`
+ * eligible columns (top > n is allowed) ends in column -1 / score NaN.  Nothing outside slots [0, top) of an output row
+ * is written (ldout >= top, in elements).  The result of a row depends on that row, the factors and its exclude bytes
+ * only: not on row0, on the panels (NBMF_PREDICT_PANEL_ROWS, as above) or on other rows; the same call twice gives
+ * the same bits.  NBMF_ERR_ARG for top outside [1, NBMF_TOP_N_MAX], rows outside [0, m), ldout < top, ldx < n with an
+ * exclude, or a NULL out_cols with nrows > 0; nrows == 0 touches nothing.  Same state rules and synchronisation as above. */
+#define NBMF_TOP_N_MAX 256
+int nbmf_top_n(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int top, int clip_theta,
+               const uint8_t* exclude, int64_t ldx, int64_t* out_cols, double* out_scores, int64_t ldout);
+
 /* Multi-GPU, one process (and one context) per GPU.  The internal matrix Y is split over the ranks along
  *   shard_axis 0: its ROWS    -> W[:, rows] is local, H is replicated; each iteration all-reduces the k x n
  *                 H-step products [P1 | P2 | loglik] (2*K*N+1 doubles) before the H-update;

@@ -9,7 +9,7 @@ from sklearn.base import BaseEstimator, TransformerMixin
 from sklearn.utils import check_array
 
 from . import _hip
-from ._solver import device_predict, device_score, nbmf_mm_restarts, nbmf_mm_solver, w_only_transform
+from ._solver import device_predict, device_score, device_top_n, nbmf_mm_restarts, nbmf_mm_solver, w_only_transform
 from ._utils import check_is_fitted
 
 # Accepted spellings of the two orientations: the exact strings of src/nbmf_mm/_base.py:127-137
@@ -227,6 +227,26 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         if np.isnan(threshold):
             raise ValueError("threshold is NaN")
         return device_predict(W, H, threshold=threshold, device=self.device)
+
+    def top_n(self, n=10, W=None, exclude=None):
+        """The ``n`` most probable features of every row of ``W`` (default ``W_``), ranked on the GPU: ``(cols, scores)``,
+        int64 and float64 of shape ``(W.shape[0], n)``.  Row i lists the features by ``predict_proba(W)[i]`` descending,
+        ties by ascending feature, and ``scores`` holds exactly those entries of ``predict_proba(W)``.  ``exclude``: a dense
+        (bool, uint8 or 0/1 numeric) or scipy-sparse matrix of shape ``(W.shape[0], n_features)`` whose nonzero entries are
+        never returned -- ``exclude=X`` means "do not recommend what the row already has".  A row with fewer than ``n``
+        features left ends in feature -1 / score NaN.  ``n`` is at most 256.  Only ``n`` entries per row come back from
+        the device instead of ``n_features``: measured figures are in DESIGN.md 4.7 (profiles/top_n_on_device.txt)."""
+        W, H = self._prediction_factors(W)
+        n = _hip.top_n_count(n, name="n")
+        if exclude is not None:
+            if not hasattr(exclude, "toarray"):
+                exclude = np.asarray(exclude)
+            if exclude.dtype != np.bool_ and not np.issubdtype(exclude.dtype, np.number):
+                raise ValueError(f"exclude must be a bool or numeric matrix (got dtype {exclude.dtype})")
+            want = (W.shape[0], H.shape[1])
+            if exclude.ndim != 2 or tuple(exclude.shape) != want:
+                raise ValueError(f"exclude has shape {tuple(exclude.shape)}, the request describes {want}")
+        return device_top_n(W, H, n, exclude=exclude, device=self.device)
 
     def impute(self, X, mask):
         """A float64 copy of ``X`` in which every entry with ``mask == 0`` is replaced by ``predict_proba`` at exactly

@@ -37,10 +37,11 @@ SYMBOLS = [
     "nbmf_set_progress", "nbmf_device_synchronize", "nbmf_small_stats", "nbmf_generate_slice", "nbmf_set_storage",
     "nbmf_set_exchange_panels", "nbmf_set_peer_timeout_ms", "nbmf_run_batch", "nbmf_batch_stats", "nbmf_sweep_info",
     "nbmf_upload_v", "nbmf_selftest_mfma_peak", "nbmf_engine_stats", "nbmf_source_hash", "nbmf_comm_info", "nbmf_cancel", "nbmf_variant_stats", "nbmf_device_bus_id",
-    "nbmf_predict_at", "nbmf_predict_rows",
+    "nbmf_predict_at", "nbmf_predict_rows", "nbmf_top_n",
 ]
 DATA_F64, DATA_U8, DATA_F32 = 0, 1, 2
 PREDICT_F64, PREDICT_U8 = 0, 1
+TOP_N_MAX = 256
 
 
 #: int fn(void* user, double* buf, int64 count) -- in-place sum over ranks on a host buffer
@@ -174,6 +175,7 @@ def load():
     lib.nbmf_selftest_unary.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p]
     lib.nbmf_predict_at.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]
     lib.nbmf_predict_rows.argtypes = [c_void_p, c_int64, c_int64, c_int, c_int, c_double, c_void_p, c_int64]
+    lib.nbmf_top_n.argtypes = [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64]
     for name in SYMBOLS:
         if name not in ("nbmf_last_error", "nbmf_source_hash"):
             getattr(lib, name).restype = c_int
@@ -246,6 +248,31 @@ def index_pairs(rows, cols):
     if rows.shape != cols.shape:
         raise ValueError(f"rows and cols must be equally long (got {rows.size} and {cols.size})")
     return np.ascontiguousarray(rows, dtype=np.int64), np.ascontiguousarray(cols, dtype=np.int64)
+
+
+def top_n_count(top, name="top"):
+    """``top`` of ``top_n`` as an int, after the checks that need no device: an integer (not a bool) in
+    ``[1, TOP_N_MAX]``.  Raises ``ValueError`` otherwise."""
+    if isinstance(top, (bool, np.bool_)) or not isinstance(top, (int, np.integer)):
+        raise ValueError(f"{name} must be an integer (got {top!r})")
+    if not 1 <= int(top) <= TOP_N_MAX:
+        raise ValueError(f"{name} must be in [1, {TOP_N_MAX}] (got {int(top)})")
+    return int(top)
+
+
+def exclude_bytes(exclude, nrows, n):
+    """The ``exclude`` array of ``top_n`` as the library takes it, with its leading dimension: ``(uint8 view, ldx)``.
+    A bool or uint8 array of shape ``(nrows, n)`` with unit stride along a row and a row stride of at least n -- a slice of
+    a wider array is passed through as it is, nothing is copied.  Raises ``ValueError`` otherwise."""
+    exclude = np.asarray(exclude)
+    if exclude.dtype != np.bool_ and exclude.dtype != np.uint8:
+        raise ValueError(f"exclude must be a bool or uint8 array (got dtype {exclude.dtype})")
+    if exclude.shape != (nrows, n):
+        raise ValueError(f"exclude must have shape ({nrows}, {n}) (got {exclude.shape})")
+    if exclude.size and ((n > 1 and exclude.strides[1] != 1) or (nrows > 1 and exclude.strides[0] < n)):
+        raise ValueError("exclude must have unit stride along a row and a row stride of at least n bytes")
+    ldx = exclude.strides[0] if exclude.size and nrows > 1 else n
+    return exclude.view(np.uint8), int(ldx)
 
 
 class Context:
@@ -454,6 +481,29 @@ class Context:
         _check(self._lib.nbmf_predict_rows(self._h, row0, nrows, int(bool(clip_theta)), PREDICT_U8 if byte_kind else PREDICT_F64,
                                            float(threshold) if byte_kind else 0.0, out.ctypes.data_as(c_void_p), int(ld)))
         return out
+
+    def top_n(self, top, row0=0, nrows=None, exclude=None, clip_theta=True, return_scores=True):
+        """The ``top`` columns with the largest Theta in each of the rows ``[row0, row0 + nrows)``, ranked on the device
+        (``nbmf_top_n``): ``(cols, scores)``, ``cols`` int64 ``(nrows, top)`` and ``scores`` float64 of the same shape (None
+        without ``return_scores``).  Slot s of a row holds the s-th column in the order "Theta descending, ties by
+        ascending column" and its Theta, bit for bit the entry :meth:`predict_rows` returns.  ``exclude``: a bool or uint8
+        array of shape ``(nrows, n)``, nonzero = never return this column (unit stride along a row, any row stride of at
+        least n: a slice of a wider array is fine).  A NaN Theta is never returned.  A row with fewer than ``top`` columns
+        left ends in column -1 / score NaN.  Only ``top`` entries per row come back from the device, not n."""
+        top = top_n_count(top)
+        row0 = int(row0)
+        nrows = self.m - row0 if nrows is None else int(nrows)
+        if row0 < 0 or nrows < 0 or row0 + nrows > self.m:
+            raise ValueError(f"rows [{row0}, {row0} + {nrows}) are not inside [0, {self.m})")
+        xptr, ldx = None, 0
+        if exclude is not None:
+            exclude, ldx = exclude_bytes(exclude, nrows, self.n)
+            xptr = exclude.ctypes.data_as(c_void_p)
+        cols = np.empty((nrows, top), dtype=np.int64)
+        scores = np.empty((nrows, top), dtype=np.float64) if return_scores else None
+        _check(self._lib.nbmf_top_n(self._h, row0, nrows, top, int(bool(clip_theta)), xptr, ldx, cols.ctypes.data_as(c_void_p),
+                                    None if scores is None else scores.ctypes.data_as(c_void_p), top))
+        return cols, scores
 
     def comm_init(self, uid: bytes, nranks: int, rank: int, shard_axis: int = 0):
         """Attach an RCCL communicator; shard_axis 0 = rows of the internal Y are split, 1 = columns."""

@@ -266,3 +266,37 @@ def device_predict(W, H, rows=None, cols=None, threshold=None, device=0):
         if rows is not None:
             return ctx.predict_at(rows, cols, clip_theta=True)
         return ctx.predict_rows(0, m, clip_theta=True, threshold=threshold)
+
+
+#: bytes of densified ``exclude`` that :func:`device_top_n` holds at a time (one row block)
+TOP_N_EXCLUDE_BLOCK_BYTES = 64 << 20
+
+
+def device_top_n(W, H, top, exclude=None, device=0):
+    """The ``top`` features with the largest Theta = clip(``W @ H``, 0, 1) for every row of ``W``, ranked on the GPU
+    (``Context.top_n``): ``(cols, scores)``, both ``(rows, top)``.  ``W``, ``H`` as in :func:`device_predict`; ``top`` and
+    ``exclude`` already validated (``_hip.top_n_count``; shape ``(rows, features)``, dense of a bool / integer / floating
+    dtype or scipy-sparse, nonzero = skip).  ``exclude`` is made dense one row block at a time, so the host never holds
+    more than ``TOP_N_EXCLUDE_BLOCK_BYTES`` of it beyond what the caller passed.  Factors only: no data is uploaded."""
+    m, k = W.shape
+    n = H.shape[1]
+    sparse = hasattr(exclude, "toarray")
+    if sparse:
+        exclude = exclude.tocsr()
+    with _hip.Context(m, n, k, device=device) as ctx:
+        ctx.set_factors(np.ascontiguousarray(W.T), H)
+        if exclude is None:
+            return ctx.top_n(top, 0, m, clip_theta=True)
+        cols = np.empty((m, top), dtype=np.int64)
+        scores = np.empty((m, top), dtype=np.float64)
+        block = max(1, min(m, TOP_N_EXCLUDE_BLOCK_BYTES // max(n, 1)))
+        for r0 in range(0, m, block):
+            nr = min(block, m - r0)
+            x = exclude[r0:r0 + nr]
+            if sparse:
+                x = (x != 0).toarray()                     # (a bool block, whatever the stored dtype)
+            x = np.asarray(x)
+            if x.dtype != np.bool_ and x.dtype != np.uint8:
+                x = x != 0
+            cols[r0:r0 + nr], scores[r0:r0 + nr] = ctx.top_n(top, r0, nr, exclude=x, clip_theta=True)
+        return cols, scores

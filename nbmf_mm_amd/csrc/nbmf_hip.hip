@@ -2509,7 +2509,7 @@ int predict_ready(nbmf_ctx* c) {
 // ------------------------------------------------------------------------------------------
 extern "C" {
 
-int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows: a compatible addition, which a caller detects by the symbol
+int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n: compatible additions, which a caller detects by the symbol
 // The sources this binary was compiled from: first 12 hex digits of the SHA-256 over nbmf_hip.hip, the *.inc files (sorted
 // by name) and include/nbmf_hip.h, put in by the Makefile (tools/src_hash.sh prints the same for the tree).  A profile or a
 // bench line that quotes it can be tied to a commit; a library built by hand without the Makefile says "unstamped".
@@ -3332,6 +3332,68 @@ int nbmf_predict_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, 
     else
       HIPCHK(hipMemcpy2DAsync(dst, (size_t)ldout * elt, panel_d, (size_t)ldd * elt, (size_t)c->n * elt, (size_t)pn,
                               hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
+  }
+  return NBMF_OK;
+}
+
+// ---- Theta ranked on the device: the top columns of each row (top_n_kernel) --------------------------------
+// Per panel: the product kernel of nbmf_predict_rows, unchanged, into the staging panel (so a score is bit for bit the
+// entry nbmf_predict_rows returns), then the selection, then top entries per row back to the host instead of n.
+int nbmf_top_n(nbmf_ctx* c, int64_t row0, int64_t nrows, int top, int clip_theta, const uint8_t* exclude, int64_t ldx,
+               int64_t* out_cols, double* out_scores, int64_t ldout) {
+  if (int rc = predict_ready(c)) return rc;
+  if (top < 1 || top > NBMF_TOP_N_MAX) return fail(NBMF_ERR_ARG, "top must be in [1, %d] (got %d)", NBMF_TOP_N_MAX, top);
+  if (nrows < 0 || row0 < 0 || row0 > c->m || nrows > c->m - row0)
+    return fail(NBMF_ERR_ARG, "rows [%lld, %lld + %lld) are not inside [0, %lld)", (long long)row0, (long long)row0, (long long)nrows,
+                (long long)c->m);
+  if (ldout < top) return fail(NBMF_ERR_ARG, "ldout %lld is less than top = %d", (long long)ldout, top);
+  if (exclude && ldx < c->n) return fail(NBMF_ERR_ARG, "ldx %lld is less than n = %lld", (long long)ldx, (long long)c->n);
+  if (nrows == 0) return NBMF_OK;
+  if (!out_cols) return fail(NBMF_ERR_ARG, "null output");
+  if (int rc = set_device(c)) return rc;
+  static_assert(NBMF_TOP_N_MAX == TN_MAX, "the kernel's entry list holds NBMF_TOP_N_MAX slots");
+  const long long n = c->n, ldd = round_up(n, 4);   // (the panel of nbmf_predict_rows, float64)
+  const long long dflt = std::max<long long>(16, (long long)((256ull << 20) / ((size_t)ldd * sizeof(double))) / 16 * 16);
+  const long long panel = std::min<long long>(nrows, std::max<long long>(1, env_int("NBMF_PREDICT_PANEL_ROWS", dflt)));
+  const long long col_groups = (c->nA + PR_WAVES * PR_STRIP - 1) / (PR_WAVES * PR_STRIP);
+  if (col_groups > 65535) return fail(NBMF_ERR_ARG, "n = %lld is beyond what nbmf_top_n launches", (long long)n);
+  PredictStage st{c->stream, {}};
+  double *panel_d = nullptr, *scores_d = nullptr;
+  long long* cols_d = nullptr;
+  unsigned char* ex_d = nullptr;
+  HIPCHK(st.get(&panel_d, sizeof(double) * (size_t)panel * ldd));
+  HIPCHK(st.get(&cols_d, sizeof(long long) * (size_t)panel * top));
+  if (out_scores) HIPCHK(st.get(&scores_d, sizeof(double) * (size_t)panel * top));
+  if (exclude) HIPCHK(st.get(&ex_d, (size_t)panel * n));
+  for (long long p0 = row0; p0 < row0 + nrows; p0 += panel) {
+    const long long pn = std::min(panel, (long long)(row0 + nrows) - p0);
+    const size_t done = (size_t)(p0 - row0);
+    if (exclude) {   // (n bytes of every row: nothing of the caller's array beyond column n - 1 is read)
+      const uint8_t* src = exclude + done * (size_t)ldx;
+      if (ldx == n)
+        HIPCHK(hipMemcpyAsync(ex_d, src, (size_t)pn * n, hipMemcpyHostToDevice, c->stream));
+      else
+        HIPCHK(hipMemcpy2DAsync(ex_d, (size_t)n, src, (size_t)ldx, (size_t)n, (size_t)pn, hipMemcpyHostToDevice, c->stream));
+    }
+    const dim3 grid((unsigned)((p0 + pn + 15) / 16 - p0 / 16), (unsigned)col_groups);
+    hipLaunchKernelGGL(predict_rows_kernel<0>, grid, dim3(PR_WAVES * 64), 0, c->stream, (const double*)c->Wn, (const double*)c->Hn,
+                       c->k, (long long)c->mA, (long long)c->nA, p0, pn, ldd, clip_theta != 0 ? 1 : 0, 0.0, (void*)panel_d);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(top_n_kernel, dim3((unsigned)pn), dim3(TN_THREADS), 0, c->stream, (const double*)panel_d, ldd, n,
+                       (const unsigned char*)ex_d, n, top, cols_d, scores_d);
+    HIPCHK(hipGetLastError());
+    const size_t w64 = sizeof(int64_t) * (size_t)top;   // (nothing of an output row beyond slot top - 1 is written)
+    if (ldout == top) {
+      HIPCHK(hipMemcpyAsync(out_cols + done * top, cols_d, (size_t)pn * w64, hipMemcpyDeviceToHost, c->stream));
+      if (out_scores) HIPCHK(hipMemcpyAsync(out_scores + done * top, scores_d, (size_t)pn * w64, hipMemcpyDeviceToHost, c->stream));
+    } else {
+      const size_t pitch = sizeof(int64_t) * (size_t)ldout;
+      HIPCHK(hipMemcpy2DAsync(out_cols + done * (size_t)ldout, pitch, cols_d, w64, w64, (size_t)pn, hipMemcpyDeviceToHost, c->stream));
+      if (out_scores)
+        HIPCHK(hipMemcpy2DAsync(out_scores + done * (size_t)ldout, pitch, scores_d, w64, w64, (size_t)pn, hipMemcpyDeviceToHost,
+                                c->stream));
+    }
     HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
   }
   return NBMF_OK;

@@ -1,5 +1,6 @@
-// nbmf_predict_kernels.inc -- Theta = W^T H handed back to the caller (nbmf_predict_at, nbmf_predict_rows; DESIGN.md 4.6).
-// Included by nbmf_hip.hip after the other kernel files.  Both kernels read the natural padded factor images
+// nbmf_predict_kernels.inc -- Theta = W^T H handed back to the caller (nbmf_predict_at, nbmf_predict_rows; DESIGN.md 4.6)
+// and ranked on the device (nbmf_top_n: top_n_kernel at the end of this file; DESIGN.md 4.7).
+// Included by nbmf_hip.hip after the other kernel files.  Both product kernels read the natural padded factor images
 // Wn[k * mA + i], Hn[k * nA + j] (what get_factor_kernel reads) and nothing else of the context; neither relies on what
 // the images hold in rows k >= K or in columns beyond m / n: components k >= K are replaced by exact zeros in registers,
 // and pad rows / columns of a tile only reach results that are never stored.
@@ -8,6 +9,8 @@ constexpr int PR_WAVES = 4;          // waves per workgroup of predict_rows_kern
 constexpr int PR_STRIP = 64;         // columns per wave: four 16-column MFMA tiles on four accumulators
 constexpr int PA_LANES = 8;          // lanes that share one pair in predict_at_kernel
 constexpr int PT_TILE = 32;          // k_major_kernel: 32 x 32 transpose tiles
+constexpr int TN_THREADS = 256;      // top_n_kernel: one workgroup per panel row, 256 columns per ordered chunk
+constexpr int TN_MAX = 256;          // most slots per row (NBMF_TOP_N_MAX): what the LDS entry list holds
 
 // Rows [prow0, prow0 + pnrows) of Theta, all n columns, into a staging panel whose row 0 is row prow0 and whose leading
 // dimension ldd is a multiple of 4 (doubles for OUT_U8 == 0, bytes otherwise).
@@ -127,5 +130,175 @@ __global__ __launch_bounds__(256) void predict_at_kernel(const double* __restric
   if (t < count && q == 0) {
     if (clip) s = s < 0.0 ? 0.0 : (s > 1.0 ? 1.0 : s);
     out[t] = s;
+  }
+}
+
+// ---- the top columns of every panel row (nbmf_top_n; DESIGN.md 4.7) ----------------------------------------------------
+// The order-preserving 64-bit key of one panel entry: a larger Theta has a larger key, equal Thetas have equal keys
+// (-0.0 and +0.0 compare equal, so they share one), and 0 is the key of an entry that may not be chosen: an excluded
+// one or a NaN.  No finite or infinite value maps to 0 (the smallest key, that of -inf, is 0x000fffffffffffff).
+__device__ __forceinline__ unsigned long long top_n_key(double v, bool skip) {
+  if (skip || v != v) return 0ull;
+  if (v == 0.0) return 1ull << 63;
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  return (b >> 63) ? ~b : (b | (1ull << 63));
+}
+
+// One workgroup per row of the staging panel predict_rows_kernel<0> has just written (row stride ldd doubles, n real
+// columns; ex: one byte per entry, row stride ldx, nonzero = skip, or null).  Slot s < top of the row's output gets the
+// column with the s-th largest Theta among the eligible ones -- ties to the lower column -- and its Theta, read back from
+// the panel; slots beyond the last eligible column get -1 and NaN.  out_cols / out_scores (may be null) are dense,
+// `top` entries per row.  Only columns j < n are ever read: what the panel holds in its pad columns does not matter.
+//
+//   1. select: eight passes over the row, 8 bits of the key at a time from the top.  Each pass counts, in a 256-bin LDS
+//      histogram (integer atomics: a count does not depend on the order), the keys that carry the digits found so far,
+//      and wave 0 scans the bins from the highest down to the one in which the running count reaches what is still
+//      needed.  The end is the key T of the last entry that gets a slot, and how many entries equal to T do (n_eq); the
+//      n_gt entries above T all do.  A row with fewer than `top` nonzero keys takes every one of them (T = 0).
+//   2. collect: one pass in ascending chunks of 256 columns with a workgroup prefix count per chunk (ballots inside a
+//      wave, wave totals through LDS), so that the entries equal to T that are taken are the n_eq FIRST ones in column
+//      order: the tie rule.  Entry lists in LDS: keys above T in slots [0, n_gt), the ties in [n_gt, n_gt + n_eq).
+//   3. sort: a bitonic network over the smallest power of two >= top, key descending, then column ascending.
+// LDS: 1 KiB of bins, 3 KiB of entries and a few counters, whatever n is.  Every branch around a barrier is uniform.
+__global__ __launch_bounds__(TN_THREADS) void top_n_kernel(const double* __restrict__ panel, long long ldd, long long n,
+                                                           const unsigned char* __restrict__ ex, long long ldx, int top,
+                                                           long long* __restrict__ out_cols, double* __restrict__ out_scores) {
+  __shared__ unsigned long long ent_key[TN_MAX];
+  __shared__ int ent_col[TN_MAX];
+  __shared__ unsigned int hist[256];
+  __shared__ unsigned int wave_cnt[2][TN_THREADS / 64][2];
+  __shared__ unsigned int sel[2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const double* __restrict__ row = panel + (size_t)blockIdx.x * ldd;
+  const unsigned char* __restrict__ exr = ex ? ex + (size_t)blockIdx.x * ldx : nullptr;
+  auto key_at = [&](long long j) { return top_n_key(row[j], exr && exr[j] != 0); };
+
+  // 1. select
+  unsigned long long prefix = 0, fixed = 0;   // the digits found so far, and the bits they occupy
+  unsigned int need = (unsigned int)top;      // slots still to fill from the keys that carry `prefix`: >= 1 throughout
+  unsigned int n_gt = 0;                      // keys above every key that carries `prefix`
+  bool all = false;
+  for (int shift = 56; shift >= 0; shift -= 8) {
+    hist[tid] = 0;
+    __syncthreads();
+    for (long long j = tid; j < n; j += TN_THREADS) {
+      const unsigned long long k = key_at(j);
+      if (k != 0 && (k & fixed) == prefix) atomicAdd(&hist[(unsigned int)(k >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (wave == 0) {   // lane l owns bins 255 - 4l .. 252 - 4l, the highest first
+      unsigned int h[4], own = 0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        h[q] = hist[255 - 4 * lane - q];
+        own += h[q];
+      }
+      unsigned int incl = own;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const unsigned int t = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += t;
+      }
+      unsigned int above = incl - own;   // keys in the bins above this lane's
+      if (lane == 63 && incl < need) {   // (first pass only: later passes scan a bin that held at least `need` keys)
+        sel[0] = 256u;
+        sel[1] = incl;
+      }
+      if (above < need && incl >= need) {   // exactly one lane: the running count reaches `need` in one of its bins
+        int d = -1;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (d < 0) {
+            if (above + h[q] >= need) d = 255 - 4 * lane - q;
+            else above += h[q];
+          }
+        sel[0] = (unsigned int)d;
+        sel[1] = above;
+      }
+    }
+    __syncthreads();
+    const unsigned int d = sel[0], above = sel[1];   // (sel is rewritten two barriers from here at the earliest)
+    n_gt += above;
+    if (d == 256u) {
+      all = true;
+      break;
+    }
+    need -= above;
+    prefix |= (unsigned long long)d << shift;
+    fixed |= 0xffull << shift;
+  }
+  const unsigned long long T = all ? 0ull : prefix;
+  const unsigned int n_eq = all ? 0u : need;
+  const unsigned int cnt = n_gt + n_eq;   // = top, or every nonzero key of a short row
+
+  // 2. collect
+  if ((unsigned int)tid >= cnt) {   // the pads of the sort: behind every real entry
+    ent_key[tid] = 0ull;
+    ent_col[tid] = 0x7fffffff;
+  }
+  const unsigned long long below = (1ull << lane) - 1ull;
+  unsigned int run_gt = 0, run_eq = 0;   // taken in the chunks before this one (the same in every thread)
+  int buf = 0;
+  for (long long c0 = 0; c0 < n; c0 += TN_THREADS, buf ^= 1) {
+    const long long j = c0 + tid;
+    const unsigned long long k = j < n ? key_at(j) : 0ull;
+    const bool gt = k > T, eq = n_eq != 0 && k == T;
+    const unsigned long long bg = __ballot(gt), be = __ballot(eq);
+    if (lane == 0) {
+      wave_cnt[buf][wave][0] = (unsigned int)__popcll(bg);
+      wave_cnt[buf][wave][1] = (unsigned int)__popcll(be);
+    }
+    __syncthreads();   // (one barrier per chunk: the next chunk writes the other half of wave_cnt)
+    unsigned int pg = run_gt + (unsigned int)__popcll(bg & below), pe = run_eq + (unsigned int)__popcll(be & below);
+#pragma unroll
+    for (int w = 0; w < TN_THREADS / 64; ++w) {
+      const unsigned int g = wave_cnt[buf][w][0], e = wave_cnt[buf][w][1];
+      if (w < wave) {
+        pg += g;
+        pe += e;
+      }
+      run_gt += g;
+      run_eq += e;
+    }
+    if (gt && pg < n_gt) {
+      ent_key[pg] = k;
+      ent_col[pg] = (int)j;
+    } else if (eq && pe < n_eq) {
+      ent_key[n_gt + pe] = k;
+      ent_col[n_gt + pe] = (int)j;
+    }
+    if (run_gt >= n_gt && run_eq >= n_eq) break;   // every slot has its entry
+  }
+  __syncthreads();
+
+  // 3. sort and write
+  int P = 2;
+  while (P < top) P <<= 1;   // <= TN_MAX
+  for (int k2 = 2; k2 <= P; k2 <<= 1)
+    for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
+      const int p = tid ^ j2;
+      if (tid < P && p > tid) {
+        const unsigned long long ka = ent_key[tid], kb = ent_key[p];
+        const int ca = ent_col[tid], cb = ent_col[p];
+        const bool a_first = ka > kb || (ka == kb && ca < cb);
+        if (((tid & k2) == 0) != a_first) {
+          ent_key[tid] = kb;
+          ent_key[p] = ka;
+          ent_col[tid] = cb;
+          ent_col[p] = ca;
+        }
+      }
+      __syncthreads();
+    }
+  if (tid < top) {
+    const size_t o = (size_t)blockIdx.x * top + tid;
+    long long col = -1;
+    double score = __longlong_as_double(0x7ff8000000000000ll);   // NaN
+    if ((unsigned int)tid < cnt) {   // (a real entry: its column is < n)
+      col = ent_col[tid];
+      score = row[col];
+    }
+    out_cols[o] = col;
+    if (out_scores) out_scores[o] = score;
   }
 }

@@ -6,10 +6,15 @@ that end in a synchronise (the library's predict calls do; NumPy's are synchrono
   (a) Theta at 2^22 seeded random index pairs: Context.predict_at against the cheapest host route (a gathered einsum over
       W[rows] and H[:, cols]) and against the only route the estimator had before (inverse_transform(W)[rows, cols]: the
       whole 69 GFLOP product and its 4.3 GB array);
-  (b) Theta for 8192 rows, as float64 and as bytes (> 0.5): Context.predict_rows against np.clip(W[:8192] @ H, 0, 1).
+  (b) Theta for 8192 rows, as float64 and as bytes (> 0.5): Context.predict_rows against np.clip(W[:8192] @ H, 0, 1);
+  (c) the top N columns of each of those 8192 rows, N = 10 and 100, with and without a 10 %-dense exclude:
+      Context.top_n against the best route there was before it (predict_rows float64, then np.argpartition and a sort of
+      the N on the host) and against the pure host route (clip(W @ H), then the same selection).
 
 The host legs are the comparison; the device path is never its own yardstick.  Before any time is taken the device and host
-results are compared at these sizes within tests/test_gpu_predict.py's bound, 2.1 K 2^-53 (|W| @ |H|) per entry.
+results are compared at these sizes within tests/test_gpu_predict.py's bound, 2.1 K 2^-53 (|W| @ |H|) per entry; the
+ranking is compared exactly with the host selection over the device's own slab (the shape has no ties).
+``--legs`` picks the legs to time (default: all three).
 Prints progress lines and, last, ONE JSON line.  Needs an MI355X: there is no CPU fallback."""
 import argparse
 import json
@@ -28,7 +33,10 @@ ap.add_argument("--k", type=int, default=64)
 ap.add_argument("--pairs", type=int, default=1 << 22)
 ap.add_argument("--rows", type=int, default=8192)
 ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--legs", default="pairs,slabs,top_n", help="comma-separated: pairs, slabs, top_n")
 args = ap.parse_args()
+legs = set(args.legs.split(","))
+assert legs <= {"pairs", "slabs", "top_n"}, f"unknown leg in {args.legs}"
 m, n, k, P, R = args.m, args.n, args.k, args.pairs, min(args.rows, args.m)
 
 
@@ -86,38 +94,74 @@ with _hip.Context(m, n, k) as ctx:
     del ref_at, dev_at, decided
 
     # ---- (a) pairs -------------------------------------------------------------------------------------------------------
-    a = {}
-    a["device_s"], a["device_all_s"] = median_s(lambda: ctx.predict_at(rows, cols))
-    say("predict_at", a["device_s"])
-    a["host_einsum_s"], a["host_einsum_all_s"] = median_s(host_einsum)
-    say("host einsum", a["host_einsum_s"])
-    a["host_inverse_transform_s"], a["host_inverse_transform_all_s"] = median_s(host_parent)
-    say("host inverse_transform", a["host_inverse_transform_s"])
-    a["gathered_factor_bytes"] = 2 * k * 8 * P
-    a["device_gathered_GBps"] = a["gathered_factor_bytes"] / a["device_s"] / 1e9
-    a["speedup_vs_einsum"] = a["host_einsum_s"] / a["device_s"]
-    a["speedup_vs_inverse_transform"] = a["host_inverse_transform_s"] / a["device_s"]
-    res["pairs_leg"] = a
+    if "pairs" in legs:
+        a = {}
+        a["device_s"], a["device_all_s"] = median_s(lambda: ctx.predict_at(rows, cols))
+        say("predict_at", a["device_s"])
+        a["host_einsum_s"], a["host_einsum_all_s"] = median_s(host_einsum)
+        say("host einsum", a["host_einsum_s"])
+        a["host_inverse_transform_s"], a["host_inverse_transform_all_s"] = median_s(host_parent)
+        say("host inverse_transform", a["host_inverse_transform_s"])
+        a["gathered_factor_bytes"] = 2 * k * 8 * P
+        a["device_gathered_GBps"] = a["gathered_factor_bytes"] / a["device_s"] / 1e9
+        a["speedup_vs_einsum"] = a["host_einsum_s"] / a["device_s"]
+        a["speedup_vs_inverse_transform"] = a["host_inverse_transform_s"] / a["device_s"]
+        res["pairs_leg"] = a
 
     # ---- (b) slabs -------------------------------------------------------------------------------------------------------
-    b = {}
-    b["device_f64_s"], b["device_f64_all_s"] = median_s(lambda: ctx.predict_rows(0, R, out=out64))
-    say("predict_rows f64", b["device_f64_s"])
-    b["device_u8_s"], b["device_u8_all_s"] = median_s(lambda: ctx.predict_rows(0, R, threshold=0.5, out=out8))
-    say("predict_rows u8", b["device_u8_s"])
-    b["host_f64_s"], b["host_f64_all_s"] = median_s(host_slab)
-    say("host slab", b["host_f64_s"])
-    b["host_u8_s"], b["host_u8_all_s"] = median_s(lambda: host_slab() > 0.5)
-    say("host slab > 0.5", b["host_u8_s"])
-    b["f64_output_bytes"], b["u8_output_bytes"] = R * n * 8, R * n
-    b["device_f64_output_GBps"] = b["f64_output_bytes"] / b["device_f64_s"] / 1e9
-    b["device_u8_output_GBps"] = b["u8_output_bytes"] / b["device_u8_s"] / 1e9
-    # The two device legs run the same product and differ in the bytes that cross PCIe (8 against 1 per entry): their
-    # difference is the time of 7/8 of the float64 copy.  An estimate derived from two end-to-end times, not a trace.
-    copy_s = max(0.0, b["device_f64_s"] - b["device_u8_s"]) * 8.0 / 7.0
-    b["f64_pcie_share_estimated"] = min(1.0, copy_s / b["device_f64_s"])
-    b["speedup_f64_vs_host"] = b["host_f64_s"] / b["device_f64_s"]
-    b["speedup_u8_vs_host"] = b["host_u8_s"] / b["device_u8_s"]
-    res["slab_leg"] = b
+    if "slabs" in legs:
+        b = {}
+        b["device_f64_s"], b["device_f64_all_s"] = median_s(lambda: ctx.predict_rows(0, R, out=out64))
+        say("predict_rows f64", b["device_f64_s"])
+        b["device_u8_s"], b["device_u8_all_s"] = median_s(lambda: ctx.predict_rows(0, R, threshold=0.5, out=out8))
+        say("predict_rows u8", b["device_u8_s"])
+        b["host_f64_s"], b["host_f64_all_s"] = median_s(host_slab)
+        say("host slab", b["host_f64_s"])
+        b["host_u8_s"], b["host_u8_all_s"] = median_s(lambda: host_slab() > 0.5)
+        say("host slab > 0.5", b["host_u8_s"])
+        b["f64_output_bytes"], b["u8_output_bytes"] = R * n * 8, R * n
+        b["device_f64_output_GBps"] = b["f64_output_bytes"] / b["device_f64_s"] / 1e9
+        b["device_u8_output_GBps"] = b["u8_output_bytes"] / b["device_u8_s"] / 1e9
+        # The two device legs run the same product and differ in the bytes that cross PCIe (8 against 1 per entry): their
+        # difference is the time of 7/8 of the float64 copy.  An estimate derived from two end-to-end times, not a trace.
+        copy_s = max(0.0, b["device_f64_s"] - b["device_u8_s"]) * 8.0 / 7.0
+        b["f64_pcie_share_estimated"] = min(1.0, copy_s / b["device_f64_s"])
+        b["speedup_f64_vs_host"] = b["host_f64_s"] / b["device_f64_s"]
+        b["speedup_u8_vs_host"] = b["host_u8_s"] / b["device_u8_s"]
+        res["slab_leg"] = b
+
+    # ---- (c) top-N ---------------------------------------------------------------------------------------------------------
+    if "top_n" in legs:
+        def host_select(theta, N, ex):
+            """The N largest of every row, ordered: argpartition, then a sort of the N (theta descending, column ascending)."""
+            if ex is not None:
+                theta = np.where(ex, -np.inf, theta)
+            part = np.argpartition(theta, n - N, axis=1)[:, n - N:]
+            vals = np.take_along_axis(theta, part, axis=1)
+            order = np.lexsort((part, -vals))
+            return np.take_along_axis(part, order, axis=1), np.take_along_axis(vals, order, axis=1)
+
+        excl = g.random((R, n)) < 0.10
+        c = {"exclude_density": float(excl.mean())}
+        for N in (10, 100):
+            for name, ex in (("plain", None), ("exclude", excl)):
+                dev_cols, dev_scores = ctx.top_n(N, 0, R, exclude=ex)
+                ctx.predict_rows(0, R, out=out64)
+                want_cols, want_scores = host_select(out64, N, ex)
+                assert np.array_equal(dev_cols, want_cols) and np.array_equal(dev_scores, want_scores), \
+                    f"top_n (N = {N}, {name}) disagrees with the host selection over predict_rows"
+                t = {}
+                t["device_s"], t["device_all_s"] = median_s(lambda: ctx.top_n(N, 0, R, exclude=ex))
+                t["predict_rows_then_host_s"], t["predict_rows_then_host_all_s"] = median_s(
+                    lambda: host_select(ctx.predict_rows(0, R, out=out64), N, ex))
+                t["host_only_s"], t["host_only_all_s"] = median_s(lambda: host_select(host_slab(), N, ex))
+                t["speedup_vs_predict_rows_then_host"] = t["predict_rows_then_host_s"] / t["device_s"]
+                t["speedup_vs_host_only"] = t["host_only_s"] / t["device_s"]
+                t["device_wins"] = bool(t["device_s"] < min(t["predict_rows_then_host_s"], t["host_only_s"]))
+                say(f"top_n N={N} {name}: device {t['device_s']:.6f} s, predict_rows + host {t['predict_rows_then_host_s']:.6f} s, "
+                    f"host only {t['host_only_s']:.6f} s")
+                c[f"N{N}_{name}"] = t
+        c["no_device_leg_loses"] = all(v["device_wins"] for v in c.values() if isinstance(v, dict))
+        res["top_n_leg"] = c
 
 print(json.dumps(res))
