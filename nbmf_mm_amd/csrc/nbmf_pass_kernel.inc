@@ -872,8 +872,18 @@ __global__ __launch_bounds__(64 * WG_WAVES, pass_wgs_per_cu(KB, DATA, MODE)) voi
               __asm__("" : "+v"(s2e));
             } else {
               // (1 - y) / t2 = it2 - y it2 in one FMA (>= 0 for y <= 1); an unobserved entry's NaN becomes the zero
-              // (1-Y).T*mask.T has there by the same v_max_f64 -- two instructions instead of three
-              s2e = max0(__builtin_fma(-y, it2, it2));
+              // (1-Y).T*mask.T has there by the same v_max_f64 -- two instructions instead of three.
+              // ">= 0" needs t2 > 0.  The select variant also serves factors off the simplex -- transform's start,
+              // _base.py:175: Theta = 8 ... 88 there -- whose t2 = 1 - Theta + eps is NEGATIVE: a max over the quotient
+              // threw every observed zero's (negative) ratio away, S1 - S2 came out as S1 alone and the step missed the
+              // reference by 1e-2 absolute (tests/test_gpu_transform_start.py).  There the max goes where the reference has
+              // its zero, on (1 - y), and the quotient keeps its sign.
+              if (TINY) {
+                s2e = max0(1.0 - y) * it2;
+                __asm__("" : "+v"(s2e));   // (kept a value of its own, as on the weighted path above)
+              } else {
+                s2e = max0(__builtin_fma(-y, it2, it2));
+              }
             }
             R1[r] = __builtin_fma(yo, it1, -s2e);   // S1 - S2
             s2 += s2e;

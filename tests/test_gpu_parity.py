@@ -420,7 +420,8 @@ def test_more_than_128_components(hip):
     np.testing.assert_allclose(a.loss_curve_, lr, rtol=LOSS_RTOL, atol=0)
     b = NBMF(n_components=k, random_state=5, max_iter=300, tol=1e-3).fit(Y, mask=mask)
     np.testing.assert_array_equal(a.components_, b.components_)
-    # evaluation sweeps and the W-only step on pinned factors (transform()'s own random start is chaotic by design)
+    # evaluation sweeps and the W-only step on pinned factors (transform()'s own un-normalised start is chaotic at a handful
+    # of components only; from it, at every layout: tests/test_gpu_transform_start.py)
     maskf = mask.astype(np.float64)
     with hip.Context(m, n, k) as ctx:
         ctx.set_hyper(1.2, 1.2)
