@@ -10,9 +10,14 @@ Parity status: PINNED.  ``oracle/make_golden.py`` imports the reference package 
 ``tests/test_oracle_golden.py`` holds this restatement to those vectors (bitwise for the
 one-step vectors and ≤1e-13 for long runs) on every CPU test run.
 
-Extensions with no reference code (Duchi projection, per-row observed-count normaliser):
-PARITY UNPINNED — specified by the reference README (README.md:27-35) and Duchi et al. 2008;
-checked by properties only.
+Extensions with no reference code (Duchi projection, per-row observed-count normaliser): there
+is nothing to pin them to but their specification -- the reference README (README.md:27-35) and
+Duchi et al. 2008.  What IS pinned is the kernels to this restatement: ``tests/duchi_start.py``
+holds ``mm_step_duchi`` to its own evaluation in long double (1e-15) and ``project_simplex_sort``
+to a transcription of the kernels' active-set loop (1e-14) from starts off the simplex, where the
+projection drops most components (``tests/test_duchi_start_cpu.py``), and
+``tests/test_gpu_duchi_start.py`` holds both Duchi kernels to it there: factors to 1e-9, loss to
+1e-10, the support exactly.
 
 Reference citations are relative to /root/reference/.
 Internal layout everywhere: Y is (m, n); W is (k, m) with columns on the simplex; H is (k, n).
@@ -230,7 +235,8 @@ def heldout_perplexity(Y, Y_hat, mask=None, eps=1e-8):
 
 
 # ----------------------------------------------------------------------------------------
-# Extensions (no reference code; PARITY UNPINNED).  Spec: /root/reference/README.md:27-35.
+# Extensions (no reference code to pin them to).  Spec: /root/reference/README.md:27-35.
+# The kernels are held to these two functions by tests/test_gpu_duchi_start.py.
 # ----------------------------------------------------------------------------------------
 
 def project_simplex_sort(v):
