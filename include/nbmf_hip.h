@@ -248,6 +248,32 @@ int nbmf_predict_rows(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int clip_theta
 int nbmf_top_n(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int top, int clip_theta,
                const uint8_t* exclude, int64_t ldx, int64_t* out_cols, double* out_scores, int64_t ldout);
 
+/* The Bernoulli log-likelihood of Theta against data, per row and per column, for the rows [row0, row0 + nrows).
+ * theta[i, j] is bit for bit the entry nbmf_predict_rows(..., clip_theta, NBMF_PREDICT_F64, ...) returns.  An entry is
+ * OBSERVED if mask is NULL or mask[(i - row0) * ldmask + j] != 0; its term is
+ *   x_kind NBMF_DATA_U8  (one byte per entry, nonzero means x = 1):  t = log(x ? theta + eps : (1 - theta) + eps)
+ *   x_kind NBMF_DATA_F64 (x in [0, 1]):                              t = x log(theta + eps) + (1 - x) log((1 - theta) + eps)
+ * with the logarithm's argument formed in exactly that order and the products and the sum of the second form rounded one
+ * by one (what NumPy computes from nbmf_predict_rows' theta), and the device library's log.  Unobserved entries contribute
+ * nothing.  row_ll[i - row0] is the sum of t over row i's observed entries and row_obs[i - row0] their count; col_ll[j] and
+ * col_obs[j] the same for column j over the call's rows.  This is the strict, observed-only sum of nbmf_loglik_strict and
+ * of examples/reproduce_magron2022.py's compute_perplexity, broken down; without a mask it is also the summand of
+ * NBMFMM.score (nbmf_loglik with clip_theta).  x and mask are nrows x n, row-major with leading dimensions ldx (elements)
+ * and ldmask (bytes), both >= n; nothing beyond column n - 1 is read.  Any of the four outputs may be NULL (not all):
+ * row outputs hold nrows entries, column outputs n.
+ * A row's result depends on that row, the factors, its data and its mask bytes only -- not on row0, on the panels or on
+ * other rows; a column's result depends on (row0, nrows), the factors and the data only, not on the panels; the same call
+ * twice gives the same bits (fixed summation orders, integer counts, no floating-point atomics).  Runs in panels like
+ * nbmf_predict_rows (NBMF_PREDICT_PANEL_ROWS, rounded up to a multiple of 16 here; panels after the first start on a
+ * multiple of 16 of the absolute row index).  NBMF_ERR_ARG for rows outside [0, m), an unknown x_kind, ldx < n, ldmask < n
+ * with a mask, a NaN or negative eps, all four outputs NULL, or a NULL x with nrows > 0; nrows == 0 reads nothing, leaves
+ * the row outputs alone and zero-fills the column outputs.  Same state rules and synchronisation as nbmf_predict_rows. */
+int nbmf_score_rows(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int clip_theta, double eps,
+                    const void* x, int x_kind /* NBMF_DATA_U8 | NBMF_DATA_F64 */, int64_t ldx,
+                    const uint8_t* mask /* NULL: all observed; nonzero = observed */, int64_t ldmask,
+                    double* row_ll, int64_t* row_obs,   /* nrows each, either may be NULL */
+                    double* col_ll, int64_t* col_obs);  /* n each, either may be NULL */
+
 /* Multi-GPU, one process (and one context) per GPU.  The internal matrix Y is split over the ranks along
  *   shard_axis 0: its ROWS    -> W[:, rows] is local, H is replicated; each iteration all-reduces the k x n
  *                 H-step products [P1 | P2 | loglik] (2*K*N+1 doubles) before the H-update;

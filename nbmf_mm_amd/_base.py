@@ -9,7 +9,8 @@ from sklearn.base import BaseEstimator, TransformerMixin
 from sklearn.utils import check_array
 
 from . import _hip
-from ._solver import device_predict, device_score, device_top_n, nbmf_mm_restarts, nbmf_mm_solver, w_only_transform
+from ._solver import (device_predict, device_score, device_score_samples, device_top_n, nbmf_mm_restarts, nbmf_mm_solver,
+                      w_only_transform)
 from ._utils import check_is_fitted
 
 # Accepted spellings of the two orientations: the exact strings of src/nbmf_mm/_base.py:127-137
@@ -283,6 +284,45 @@ class NBMFMM(BaseEstimator, TransformerMixin):
     def perplexity(self, X, mask=None):
         """exp(-score) (_base.py:249-265)."""
         return np.exp(-self.score(X, mask))
+
+    def score_samples(self, X, mask=None, W=None, axis=0, return_counts=False):
+        """Mean log-likelihood per observed entry of every row of ``X`` (``axis=0``) or of every feature (``axis=1``) under
+        ``predict_proba(W)``, summed on the GPU: a float64 1-D array, NaN where nothing is observed; with
+        ``return_counts`` also the int64 counts of observed entries, ``(scores, counts)``.  The summand is :meth:`score`'s
+        (``x log(theta + 1e-8) + (1 - x) log(1 - theta + 1e-8)``) over observed entries only.  ``W`` defaults to ``W_``
+        and ``X`` then has the fitted shape; with ``W`` given (``transform`` the new rows first) ``X`` has ``W.shape[0]``
+        rows.  Unlike :meth:`score` nothing here draws from an RNG: the result is a function of the factors and the data.
+        ``mask``: dense or scipy-sparse of X's shape, of any numeric dtype: nonzero = observed.  Sparse or float input is
+        streamed in row blocks; feature scores of block-streamed input equal the one-call result to rounding, row scores
+        bit for bit.  Only rows + features numbers leave the device, and X goes up at one byte per entry when it is
+        binary.  Measured on an MI355X at 65536 x 8192, K = 64 (profiles/score_samples_on_device.txt): 8192 rows
+        of uint8 data under a 90 % mask, rows and features, in 3.2 ms against 557 ms for ``predict_proba`` plus NumPy; 0.48 ms
+        of it is the kernel, the rest mostly the upload of X and mask."""
+        W, H = self._prediction_factors(W)
+        if axis not in (0, 1) or isinstance(axis, (bool, np.bool_)):
+            raise ValueError(f"axis must be 0 (rows) or 1 (features) (got {axis!r})")
+        X = self._validated(X, keep_sparse=True)
+        want = (W.shape[0], H.shape[1])
+        if tuple(X.shape) != want:
+            raise ValueError(f"X has shape {tuple(X.shape)}, the request describes {want}")
+        if hasattr(X, "toarray"):
+            if X.nnz and not (X.data.min() >= 0 and X.data.max() <= 1):
+                raise ValueError("X must be binary")                  # fit's check of the stored values
+        elif X.dtype != np.bool_ and not np.all((X >= 0) & (X <= 1)):
+            if X.dtype != np.uint8:
+                check_array(X, dtype=None)                            # NaN / inf: sklearn's own error first, as in fit
+            raise ValueError("X must be binary")
+        if mask is not None:
+            if not hasattr(mask, "toarray"):
+                mask = np.asarray(mask)
+            if mask.dtype != np.bool_ and not np.issubdtype(mask.dtype, np.number):
+                raise ValueError(f"mask must be a bool or numeric matrix (got dtype {mask.dtype})")
+            if mask.ndim != 2 or tuple(mask.shape) != want:
+                raise ValueError(f"mask has shape {tuple(mask.shape)}, the request describes {want}")
+        sums, counts = device_score_samples(W, H, X, mask=mask, axis=int(axis), device=self.device)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            scores = np.where(counts > 0, sums / np.maximum(counts, 1), np.nan)
+        return (scores, counts) if return_counts else scores
 
 
 # alias kept for backwards compatibility (_base.py:269)

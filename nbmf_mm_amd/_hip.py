@@ -37,7 +37,7 @@ SYMBOLS = [
     "nbmf_set_progress", "nbmf_device_synchronize", "nbmf_small_stats", "nbmf_generate_slice", "nbmf_set_storage",
     "nbmf_set_exchange_panels", "nbmf_set_peer_timeout_ms", "nbmf_run_batch", "nbmf_batch_stats", "nbmf_sweep_info",
     "nbmf_upload_v", "nbmf_selftest_mfma_peak", "nbmf_engine_stats", "nbmf_source_hash", "nbmf_comm_info", "nbmf_cancel", "nbmf_variant_stats", "nbmf_device_bus_id",
-    "nbmf_predict_at", "nbmf_predict_rows", "nbmf_top_n",
+    "nbmf_predict_at", "nbmf_predict_rows", "nbmf_top_n", "nbmf_score_rows",
 ]
 DATA_F64, DATA_U8, DATA_F32 = 0, 1, 2
 PREDICT_F64, PREDICT_U8 = 0, 1
@@ -176,6 +176,8 @@ def load():
     lib.nbmf_predict_at.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]
     lib.nbmf_predict_rows.argtypes = [c_void_p, c_int64, c_int64, c_int, c_int, c_double, c_void_p, c_int64]
     lib.nbmf_top_n.argtypes = [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64]
+    lib.nbmf_score_rows.argtypes = [c_void_p, c_int64, c_int64, c_int, c_double, c_void_p, c_int, c_int64, c_void_p, c_int64,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]
     for name in SYMBOLS:
         if name not in ("nbmf_last_error", "nbmf_source_hash"):
             getattr(lib, name).restype = c_int
@@ -273,6 +275,25 @@ def exclude_bytes(exclude, nrows, n):
         raise ValueError("exclude must have unit stride along a row and a row stride of at least n bytes")
     ldx = exclude.strides[0] if exclude.size and nrows > 1 else n
     return exclude.view(np.uint8), int(ldx)
+
+
+def score_panel(a, nrows, n, name="x", byte_only=False):
+    """The data (or, ``byte_only``, the mask) of ``score_rows`` as the library takes it: ``(array, kind, ld)``, ``kind``
+    DATA_U8 (a bool or uint8 array, returned as its uint8 view) or DATA_F64 and ``ld`` the leading dimension in elements.
+    Shape ``(nrows, n)``, unit stride along a row and a row stride of at least n elements -- a slice of a wider array is
+    passed through as it is, nothing is copied.  Raises ``ValueError`` otherwise."""
+    a = np.asarray(a)
+    byte_kind = a.dtype == np.bool_ or a.dtype == np.uint8
+    if not byte_kind and (byte_only or a.dtype != np.float64):
+        kinds = "a bool or uint8" if byte_only else "a bool, uint8 or float64"
+        raise ValueError(f"{name} must be {kinds} array (got dtype {a.dtype})")
+    if a.shape != (nrows, n):
+        raise ValueError(f"{name} must have shape ({nrows}, {n}) (got {a.shape})")
+    size = a.itemsize
+    if a.size and ((n > 1 and a.strides[1] != size) or (nrows > 1 and (a.strides[0] < n * size or a.strides[0] % size))):
+        raise ValueError(f"{name} must have unit stride along a row and a row stride of at least n elements")
+    ld = a.strides[0] // size if a.size and nrows > 1 else n
+    return (a.view(np.uint8), DATA_U8, int(ld)) if byte_kind else (a, DATA_F64, int(ld))
 
 
 class Context:
@@ -504,6 +525,38 @@ class Context:
         _check(self._lib.nbmf_top_n(self._h, row0, nrows, top, int(bool(clip_theta)), xptr, ldx, cols.ctypes.data_as(c_void_p),
                                     None if scores is None else scores.ctypes.data_as(c_void_p), top))
         return cols, scores
+
+    def score_rows(self, x, mask=None, row0=0, nrows=None, clip_theta=True, eps=1e-8, rows=True, cols=False):
+        """The Bernoulli log-likelihood of Theta against the data ``x`` of the rows ``[row0, row0 + nrows)``, summed per
+        row and / or per column on the device (``nbmf_score_rows``): ``(row_ll, row_obs, col_ll, col_obs)``, float64 sums and
+        int64 counts of the observed entries, ``nrows`` long for the rows and ``n`` long for the columns; None for the pair
+        not asked for (``rows`` / ``cols``).  ``x``: shape ``(nrows, n)``, bool / uint8 (nonzero means 1; the term is
+        ``log(x ? theta + eps : (1 - theta) + eps)``) or float64 in [0, 1] (``x log(theta + eps) + (1 - x) log((1 - theta)
+        + eps)``).  ``mask``: bool / uint8 of the same shape, nonzero = observed; None: every entry.  Both may be slices of
+        wider arrays (unit stride along a row); nothing is copied on the host.  Theta is bit for bit what
+        :meth:`predict_rows` returns.  Only ``nrows + n`` sums and counts come back from the device."""
+        row0 = int(row0)
+        nrows = self.m - row0 if nrows is None else int(nrows)
+        if row0 < 0 or nrows < 0 or row0 + nrows > self.m:
+            raise ValueError(f"rows [{row0}, {row0} + {nrows}) are not inside [0, {self.m})")
+        if not rows and not cols:
+            raise ValueError("nothing requested: rows and cols are both false")
+        eps = float(eps)
+        if not eps >= 0.0:
+            raise ValueError(f"eps must be >= 0 (got {eps})")
+        x, x_kind, ldx = score_panel(x, nrows, self.n, "x")
+        mptr, ldm = None, 0
+        if mask is not None:
+            mask, _, ldm = score_panel(mask, nrows, self.n, "mask", byte_only=True)
+            mptr = mask.ctypes.data_as(c_void_p)
+        row_ll = np.empty(nrows, dtype=np.float64) if rows else None
+        row_obs = np.empty(nrows, dtype=np.int64) if rows else None
+        col_ll = np.empty(self.n, dtype=np.float64) if cols else None
+        col_obs = np.empty(self.n, dtype=np.int64) if cols else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(c_void_p)   # noqa: E731
+        _check(self._lib.nbmf_score_rows(self._h, row0, nrows, int(bool(clip_theta)), eps, ptr(x), x_kind, ldx, mptr, ldm,
+                                         ptr(row_ll), ptr(row_obs), ptr(col_ll), ptr(col_obs)))
+        return row_ll, row_obs, col_ll, col_obs
 
     def comm_init(self, uid: bytes, nranks: int, rank: int, shard_axis: int = 0):
         """Attach an RCCL communicator; shard_axis 0 = rows of the internal Y are split, 1 = columns."""

@@ -300,3 +300,64 @@ def device_top_n(W, H, top, exclude=None, device=0):
                 x = x != 0
             cols[r0:r0 + nr], scores[r0:r0 + nr] = ctx.top_n(top, r0, nr, exclude=x, clip_theta=True)
         return cols, scores
+
+
+#: bytes of data (and as many of mask) that :func:`device_score_samples` converts or makes dense at a time (one row block)
+SCORE_SAMPLES_BLOCK_BYTES = 64 << 20
+
+
+def _score_block(A, r0, nr, is_mask):
+    """Rows ``[r0, r0 + nr)`` of the data or the mask as ``Context.score_rows`` takes them.  A bool / uint8 block is
+    passed as it is; a mask of another dtype as ``!= 0``; other data as uint8 when the block is exactly {0, 1}, else as
+    float64.  A sparse block is made dense first; a block that is not laid out row after row is copied."""
+    a = A[r0:r0 + nr]
+    if hasattr(a, "toarray"):
+        a = (a != 0).toarray() if is_mask else a.toarray()
+    a = np.asarray(a)
+    if a.dtype != np.bool_ and a.dtype != np.uint8:
+        if is_mask:
+            a = a != 0
+        elif np.all((a == 0) | (a == 1)):
+            a = a.astype(np.uint8)
+        else:
+            a = np.asarray(a, dtype=np.float64)
+    if a.size and (a.strides[1] != a.itemsize or a.strides[0] < a.shape[1] * a.itemsize or a.strides[0] % a.itemsize):
+        a = np.ascontiguousarray(a)
+    return a
+
+
+def device_score_samples(W, H, X, mask=None, axis=0, device=0):
+    """The log-likelihood of Theta = clip(``W @ H``, 0, 1) against ``X`` (eps = 1e-8, as ``NBMFMM.score``), summed on the
+    GPU (``Context.score_rows``) over the observed entries of every row (``axis=0``) or of every feature (``axis=1``):
+    ``(sums float64, counts int64)``.  ``W``, ``H`` as in :func:`device_predict`; ``X`` and ``mask`` (nonzero = observed)
+    dense or scipy-sparse of shape ``(rows, features)``, already validated.  Factors only: no context holds the data.
+    Dense bool / uint8 input with a bool / uint8 (or no) mask goes to the device in one call as it is.  Anything else goes
+    in row blocks of at most ``SCORE_SAMPLES_BLOCK_BYTES`` (a multiple of 16 rows): sparse blocks are made dense, float
+    data goes as uint8 where the block is exactly {0, 1} and as float64 otherwise.  A row's result does not depend on the
+    blocks.  For ``axis=1`` the blocks' sums and counts are added on the host in ascending order: feature scores of
+    block-streamed input equal the one-call result to rounding, not bit for bit."""
+    m, k = W.shape
+    n = H.shape[1]
+    byte = lambda a: a is None or (not hasattr(a, "toarray") and a.dtype in (np.bool_, np.uint8))   # noqa: E731
+    if hasattr(X, "toarray"):
+        X = X.tocsr()
+    elif not isinstance(X, np.ndarray):
+        X = np.asarray(X)
+    if mask is not None:
+        mask = mask.tocsr() if hasattr(mask, "toarray") else np.asarray(mask)
+    block = m if byte(X) and byte(mask) else max(16, SCORE_SAMPLES_BLOCK_BYTES // (8 * max(n, 1)) // 16 * 16)
+    sums = np.zeros(n if axis else m, dtype=np.float64)
+    counts = np.zeros(n if axis else m, dtype=np.int64)
+    with _hip.Context(m, n, k, device=device) as ctx:
+        ctx.set_factors(np.ascontiguousarray(W.T), H)
+        for r0 in range(0, m, max(block, 1)):
+            nr = min(block, m - r0)
+            x = _score_block(X, r0, nr, False)
+            mk = None if mask is None else _score_block(mask, r0, nr, True)
+            rl, ro, cl, co = ctx.score_rows(x, mk, r0, nr, clip_theta=True, eps=1e-8, rows=not axis, cols=bool(axis))
+            if axis:
+                sums += cl
+                counts += co
+            else:
+                sums[r0:r0 + nr], counts[r0:r0 + nr] = rl, ro
+    return sums, counts

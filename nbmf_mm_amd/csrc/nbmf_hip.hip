@@ -320,6 +320,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 #include "nbmf_peer_kernels.inc"
 #include "nbmf_small_kernel.inc"
 #include "nbmf_predict_kernels.inc"
+#include "nbmf_score_kernels.inc"
 
 }  // namespace
 
@@ -2509,7 +2510,7 @@ int predict_ready(nbmf_ctx* c) {
 // ------------------------------------------------------------------------------------------
 extern "C" {
 
-int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n: compatible additions, which a caller detects by the symbol
+int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows: compatible additions, which a caller detects by the symbol
 // The sources this binary was compiled from: first 12 hex digits of the SHA-256 over nbmf_hip.hip, the *.inc files (sorted
 // by name) and include/nbmf_hip.h, put in by the Makefile (tools/src_hash.sh prints the same for the tree).  A profile or a
 // bench line that quotes it can be tied to a commit; a library built by hand without the Makefile says "unstamped".
@@ -3396,6 +3397,116 @@ int nbmf_top_n(nbmf_ctx* c, int64_t row0, int64_t nrows, int top, int clip_theta
     }
     HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
   }
+  return NBMF_OK;
+}
+
+// ---- Theta judged against data: log-likelihood per row and per column (nbmf_score_kernels.inc) -------------
+// Per panel: the caller's data and mask rows up into staging panels of leading dimension round_up(n, 4) (n bytes or
+// doubles of every row: nothing beyond column n - 1 is read), the fused product-and-score kernel, then the finishing
+// steps -- the strips of a row in ascending order, the 16-row blocks of a column in ascending order onto accumulators that
+// stay on the device for the whole call.  Panels after the first start on a multiple of 16 of the absolute row index, so a
+// 16-row block never straddles two panels and a column's chain of additions is the same whatever the panel height.
+int nbmf_score_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, double eps, const void* x, int x_kind, int64_t ldx,
+                    const uint8_t* mask, int64_t ldmask, double* row_ll, int64_t* row_obs, double* col_ll, int64_t* col_obs) {
+  if (int rc = predict_ready(c)) return rc;
+  if (nrows < 0 || row0 < 0 || row0 > c->m || nrows > c->m - row0)
+    return fail(NBMF_ERR_ARG, "rows [%lld, %lld + %lld) are not inside [0, %lld)", (long long)row0, (long long)row0, (long long)nrows,
+                (long long)c->m);
+  if (x_kind != NBMF_DATA_U8 && x_kind != NBMF_DATA_F64) return fail(NBMF_ERR_ARG, "unknown x_kind %d", x_kind);
+  if (ldx < c->n) return fail(NBMF_ERR_ARG, "ldx %lld is less than n = %lld", (long long)ldx, (long long)c->n);
+  if (mask && ldmask < c->n) return fail(NBMF_ERR_ARG, "ldmask %lld is less than n = %lld", (long long)ldmask, (long long)c->n);
+  if (!(eps >= 0.0)) return fail(NBMF_ERR_ARG, "eps must be >= 0 (got %g)", eps);
+  if (!row_ll && !row_obs && !col_ll && !col_obs) return fail(NBMF_ERR_ARG, "no output requested");
+  const long long n = c->n;
+  if (nrows == 0) {   // nothing is read; the sums over no rows
+    if (col_ll) std::fill(col_ll, col_ll + n, 0.0);
+    if (col_obs) std::fill(col_obs, col_obs + n, (int64_t)0);
+    return NBMF_OK;
+  }
+  if (!x) return fail(NBMF_ERR_ARG, "null data");
+  if (int rc = set_device(c)) return rc;
+  const bool want_rows = row_ll || row_obs, want_cols = col_ll || col_obs;
+  const size_t elt = x_kind == NBMF_DATA_F64 ? sizeof(double) : 1;
+  const long long ldp = round_up(n, 4);                        // (<= nA) the staged panels' leading dimension
+  const long long strips = (n + PR_STRIP - 1) / PR_STRIP;      // the strips that hold a real column
+  const long long col_groups = (c->nA + PR_WAVES * PR_STRIP - 1) / (PR_WAVES * PR_STRIP);
+  if (col_groups > 65535) return fail(NBMF_ERR_ARG, "n = %lld is beyond what nbmf_score_rows launches", (long long)n);
+  // the budget of nbmf_predict_rows over everything a panel row stages: data, mask, its strip partials, its share of a block's
+  const size_t per_row = (size_t)ldp * (elt + (mask ? 1 : 0)) + (want_rows ? (size_t)strips * 12 + 16 : 0) +
+                         (want_cols ? ((size_t)ldp * 12 + 15) / 16 : 0);
+  const long long dflt = std::max<long long>(16, (long long)((256ull << 20) / per_row) / 16 * 16);
+  const long long panel = round_up(std::max<long long>(1, env_int("NBMF_PREDICT_PANEL_ROWS", dflt)), 16);
+  const long long stage_rows = std::min<long long>(panel, nrows);   // (no panel holds more rows than either)
+  const long long max_blocks = stage_rows / 16 + 2;                 // (... nor touches more 16-row blocks than this)
+  PredictStage st{c->stream, {}};
+  char* x_d = nullptr;
+  unsigned char* m_d = nullptr;
+  double *rpart_d = nullptr, *cpart_d = nullptr, *row_ll_d = nullptr, *col_ll_d = nullptr;
+  int *rcnt_d = nullptr, *ccnt_d = nullptr;
+  long long *row_obs_d = nullptr, *col_obs_d = nullptr;
+  HIPCHK(st.get(&x_d, (size_t)stage_rows * ldp * elt));
+  if (mask) HIPCHK(st.get(&m_d, (size_t)stage_rows * ldp));
+  if (want_rows) {
+    HIPCHK(st.get(&rpart_d, sizeof(double) * (size_t)strips * stage_rows));
+    HIPCHK(st.get(&rcnt_d, sizeof(int) * (size_t)strips * stage_rows));
+    HIPCHK(st.get(&row_ll_d, sizeof(double) * (size_t)stage_rows));
+    HIPCHK(st.get(&row_obs_d, sizeof(long long) * (size_t)stage_rows));
+  }
+  if (want_cols) {
+    HIPCHK(st.get(&cpart_d, sizeof(double) * (size_t)max_blocks * ldp));
+    HIPCHK(st.get(&ccnt_d, sizeof(int) * (size_t)max_blocks * ldp));
+    HIPCHK(st.get(&col_ll_d, sizeof(double) * (size_t)n));
+    HIPCHK(st.get(&col_obs_d, sizeof(long long) * (size_t)n));
+    HIPCHK(hipMemsetAsync(col_ll_d, 0, sizeof(double) * (size_t)n, c->stream));
+    HIPCHK(hipMemsetAsync(col_obs_d, 0, sizeof(long long) * (size_t)n, c->stream));
+  }
+  const long long end = row0 + nrows;
+  for (long long p0 = row0; p0 < end;) {
+    const long long pn = std::min(panel - p0 % 16, end - p0);   // (p0 + pn is a multiple of 16, or the end)
+    const size_t done = (size_t)(p0 - row0);
+    const char* xsrc = (const char*)x + done * (size_t)ldx * elt;
+    if (ldx == n && ldp == n)
+      HIPCHK(hipMemcpyAsync(x_d, xsrc, (size_t)pn * n * elt, hipMemcpyHostToDevice, c->stream));
+    else
+      HIPCHK(hipMemcpy2DAsync(x_d, (size_t)ldp * elt, xsrc, (size_t)ldx * elt, (size_t)n * elt, (size_t)pn, hipMemcpyHostToDevice,
+                              c->stream));
+    if (mask) {
+      const uint8_t* msrc = mask + done * (size_t)ldmask;
+      if (ldmask == n && ldp == n)
+        HIPCHK(hipMemcpyAsync(m_d, msrc, (size_t)pn * n, hipMemcpyHostToDevice, c->stream));
+      else
+        HIPCHK(hipMemcpy2DAsync(m_d, (size_t)ldp, msrc, (size_t)ldmask, (size_t)n, (size_t)pn, hipMemcpyHostToDevice, c->stream));
+    }
+    const long long blocks = (p0 + pn + 15) / 16 - p0 / 16;   // (<= max_blocks)
+    const dim3 grid((unsigned)blocks, (unsigned)col_groups);
+    if (x_kind == NBMF_DATA_F64)
+      hipLaunchKernelGGL(score_rows_kernel<1>, grid, dim3(PR_WAVES * 64), 0, c->stream, (const double*)c->Wn, (const double*)c->Hn,
+                         c->k, (long long)c->mA, (long long)c->nA, n, p0, pn, ldp, clip_theta != 0 ? 1 : 0, eps, (const void*)x_d,
+                         (const unsigned char*)m_d, rpart_d, rcnt_d, cpart_d, ccnt_d);
+    else
+      hipLaunchKernelGGL(score_rows_kernel<0>, grid, dim3(PR_WAVES * 64), 0, c->stream, (const double*)c->Wn, (const double*)c->Hn,
+                         c->k, (long long)c->mA, (long long)c->nA, n, p0, pn, ldp, clip_theta != 0 ? 1 : 0, eps, (const void*)x_d,
+                         (const unsigned char*)m_d, rpart_d, rcnt_d, cpart_d, ccnt_d);
+    HIPCHK(hipGetLastError());
+    if (want_rows) {
+      hipLaunchKernelGGL(score_rows_finish_kernel, dim3((unsigned)((pn + 255) / 256)), dim3(256), 0, c->stream,
+                         (const double*)rpart_d, (const int*)rcnt_d, pn, strips, row_ll_d, row_obs_d);
+      HIPCHK(hipGetLastError());
+      if (row_ll) HIPCHK(hipMemcpyAsync(row_ll + done, row_ll_d, sizeof(double) * (size_t)pn, hipMemcpyDeviceToHost, c->stream));
+      if (row_obs)
+        HIPCHK(hipMemcpyAsync(row_obs + done, row_obs_d, sizeof(int64_t) * (size_t)pn, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (want_cols) {
+      hipLaunchKernelGGL(score_cols_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
+                         (const double*)cpart_d, (const int*)ccnt_d, blocks, ldp, n, col_ll_d, col_obs_d);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
+    p0 += pn;
+  }
+  if (col_ll) HIPCHK(hipMemcpyAsync(col_ll, col_ll_d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  if (col_obs) HIPCHK(hipMemcpyAsync(col_obs, col_obs_d, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  if (want_cols) HIPCHK(hipStreamSynchronize(c->stream));
   return NBMF_OK;
 }
 

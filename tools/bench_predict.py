@@ -13,8 +13,9 @@ that end in a synchronise (the library's predict calls do; NumPy's are synchrono
 
 The host legs are the comparison; the device path is never its own yardstick.  Before any time is taken the device and host
 results are compared at these sizes within tests/test_gpu_predict.py's bound, 2.1 K 2^-53 (|W| @ |H|) per entry; the
-ranking is compared exactly with the host selection over the device's own slab (the shape has no ties).
-``--legs`` picks the legs to time (default: all three).
+ranking is compared exactly with the host selection over the device's own slab (the shape has no ties); the score sums are
+compared with the host's over the device's own slab within tests/test_gpu_score_samples.py's bound plus NumPy's own
+summation error.  ``--legs`` picks the legs to time (default: all four).
 Prints progress lines and, last, ONE JSON line.  Needs an MI355X: there is no CPU fallback."""
 import argparse
 import json
@@ -33,10 +34,10 @@ ap.add_argument("--k", type=int, default=64)
 ap.add_argument("--pairs", type=int, default=1 << 22)
 ap.add_argument("--rows", type=int, default=8192)
 ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--legs", default="pairs,slabs,top_n", help="comma-separated: pairs, slabs, top_n")
+ap.add_argument("--legs", default="pairs,slabs,top_n,score_samples", help="comma-separated: pairs, slabs, top_n, score_samples")
 args = ap.parse_args()
 legs = set(args.legs.split(","))
-assert legs <= {"pairs", "slabs", "top_n"}, f"unknown leg in {args.legs}"
+assert legs <= {"pairs", "slabs", "top_n", "score_samples"}, f"unknown leg in {args.legs}"
 m, n, k, P, R = args.m, args.n, args.k, args.pairs, min(args.rows, args.m)
 
 
@@ -163,5 +164,44 @@ with _hip.Context(m, n, k) as ctx:
                 c[f"N{N}_{name}"] = t
         c["no_device_leg_loses"] = all(v["device_wins"] for v in c.values() if isinstance(v, dict))
         res["top_n_leg"] = c
+
+    # ---- (d) score_samples ---------------------------------------------------------------------------------------------------
+    if "score_samples" in legs:
+        eps = 1e-8
+        X = g.random((R, n)) < 0.25
+        mask = g.random((R, n)) < 0.90
+
+        def host_scores():
+            """predict_rows, then the same sums on the host: one logarithm per entry, as the device forms it."""
+            theta = ctx.predict_rows(0, R, out=out64)
+            t = np.where(mask, np.log(np.where(X, theta + eps, (1.0 - theta) + eps)), 0.0)
+            return t.sum(1), mask.sum(1), t.sum(0), mask.sum(0), t
+
+        d = {"data": "uint8", "observed": float(mask.mean()), "input_bytes": 2 * R * n, "output_bytes": 16 * (R + n)}
+        got = ctx.score_rows(X, mask, 0, R, rows=True, cols=True)
+        want = host_scores()
+        absum = np.abs(want[4])
+        for name, ll, obs, w_ll, w_obs, w_abs in (("rows", got[0], got[1], want[0], want[1], absum.sum(1)),
+                                                  ("cols", got[2], got[3], want[2], want[3], absum.sum(0))):
+            assert np.array_equal(obs, w_obs), f"score_rows: the {name} counts disagree with the host"
+            # the tests' bound against an exactly rounded sum, plus NumPy's pairwise summation (at most c 2^-53 sum|t|)
+            worst = float(np.max(np.abs(ll - w_ll) / ((1.5 * w_obs + 8) * 2.0 ** -52 * w_abs)))
+            assert worst <= 1.0, f"score_rows: the {name} sums are {worst} bounds away from the host's"
+            d[f"{name}_worst_over_bound"] = worst
+        del want, absum
+        d["device_s"], d["device_all_s"] = median_s(lambda: ctx.score_rows(X, mask, 0, R, rows=True, cols=True))
+        say("score_rows rows + cols", d["device_s"])
+        d["device_rows_only_s"], d["device_rows_only_all_s"] = median_s(lambda: ctx.score_rows(X, mask, 0, R))
+        say("score_rows rows", d["device_rows_only_s"])
+        d["device_no_mask_s"], d["device_no_mask_all_s"] = median_s(lambda: ctx.score_rows(X, None, 0, R, rows=True, cols=True))
+        say("score_rows without a mask", d["device_no_mask_s"])
+        d["predict_rows_then_host_s"], d["predict_rows_then_host_all_s"] = median_s(host_scores)
+        say("predict_rows + host sums", d["predict_rows_then_host_s"])
+        d["device_input_GBps"] = d["input_bytes"] / d["device_s"] / 1e9
+        # the call with and without the mask differs by one of the two byte panels that cross PCIe: twice the difference
+        # estimates the upload's share of the call.  Derived from two end-to-end times, not a trace.
+        d["upload_share_estimated"] = min(1.0, 2.0 * max(0.0, d["device_s"] - d["device_no_mask_s"]) / d["device_s"])
+        d["speedup_vs_predict_rows_then_host"] = d["predict_rows_then_host_s"] / d["device_s"]
+        res["score_samples_leg"] = d
 
 print(json.dumps(res))
