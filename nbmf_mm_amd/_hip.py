@@ -262,38 +262,30 @@ def top_n_count(top, name="top"):
     return int(top)
 
 
-def exclude_bytes(exclude, nrows, n):
-    """The ``exclude`` array of ``top_n`` as the library takes it, with its leading dimension: ``(uint8 view, ldx)``.
-    A bool or uint8 array of shape ``(nrows, n)`` with unit stride along a row and a row stride of at least n -- a slice of
-    a wider array is passed through as it is, nothing is copied.  Raises ``ValueError`` otherwise."""
-    exclude = np.asarray(exclude)
-    if exclude.dtype != np.bool_ and exclude.dtype != np.uint8:
-        raise ValueError(f"exclude must be a bool or uint8 array (got dtype {exclude.dtype})")
-    if exclude.shape != (nrows, n):
-        raise ValueError(f"exclude must have shape ({nrows}, {n}) (got {exclude.shape})")
-    if exclude.size and ((n > 1 and exclude.strides[1] != 1) or (nrows > 1 and exclude.strides[0] < n)):
-        raise ValueError("exclude must have unit stride along a row and a row stride of at least n bytes")
-    ldx = exclude.strides[0] if exclude.size and nrows > 1 else n
-    return exclude.view(np.uint8), int(ldx)
+#: the dtypes a row array may have: one byte per entry (passed to the library as uint8), or float64
+BYTE_KINDS = (np.bool_, np.uint8)
+ANY_KINDS = BYTE_KINDS + (np.float64,)
 
 
-def score_panel(a, nrows, n, name="x", byte_only=False):
-    """The data (or, ``byte_only``, the mask) of ``score_rows`` as the library takes it: ``(array, kind, ld)``, ``kind``
-    DATA_U8 (a bool or uint8 array, returned as its uint8 view) or DATA_F64 and ``ld`` the leading dimension in elements.
-    Shape ``(nrows, n)``, unit stride along a row and a row stride of at least n elements -- a slice of a wider array is
-    passed through as it is, nothing is copied.  Raises ``ValueError`` otherwise."""
+def row_array(a, nrows, n, name, kinds):
+    """A caller's ``(nrows, n)`` array as the row-slab calls of the library take it -- the ``out`` of ``predict_rows``,
+    the ``exclude`` of ``top_n``, the data and the mask of ``score_rows``: ``(array, kind, ld)``, ``kind`` DATA_U8 (a bool
+    or uint8 array, returned as its uint8 view) or DATA_F64, ``ld`` the leading dimension in elements.  The dtype must be
+    one of ``kinds`` (BYTE_KINDS, ANY_KINDS or ``(np.float64,)``), the shape ``(nrows, n)``, the stride along a row one
+    element, the row stride at least n elements and whole elements -- a slice of a wider array is passed through as it is,
+    nothing is copied.  The row stride of a single row or of an empty array is ignored: ``ld = n``.  Raises ``ValueError``
+    otherwise."""
     a = np.asarray(a)
-    byte_kind = a.dtype == np.bool_ or a.dtype == np.uint8
-    if not byte_kind and (byte_only or a.dtype != np.float64):
-        kinds = "a bool or uint8" if byte_only else "a bool, uint8 or float64"
-        raise ValueError(f"{name} must be {kinds} array (got dtype {a.dtype})")
+    if a.dtype not in kinds:
+        *first, last = [np.dtype(t).name for t in kinds]          # "bool, uint8 or float64"
+        raise ValueError(f"{name} must be a {', '.join(first) + ' or ' if first else ''}{last} array (got dtype {a.dtype})")
     if a.shape != (nrows, n):
         raise ValueError(f"{name} must have shape ({nrows}, {n}) (got {a.shape})")
     size = a.itemsize
     if a.size and ((n > 1 and a.strides[1] != size) or (nrows > 1 and (a.strides[0] < n * size or a.strides[0] % size))):
         raise ValueError(f"{name} must have unit stride along a row and a row stride of at least n elements")
     ld = a.strides[0] // size if a.size and nrows > 1 else n
-    return (a.view(np.uint8), DATA_U8, int(ld)) if byte_kind else (a, DATA_F64, int(ld))
+    return (a.view(np.uint8), DATA_U8, int(ld)) if a.dtype != np.float64 else (a, DATA_F64, int(ld))
 
 
 class Context:
@@ -480,27 +472,30 @@ class Context:
                                          int(bool(clip_theta)), out.ctypes.data_as(c_void_p)))
         return out
 
+    def _rows(self, row0, nrows):
+        """``(row0, nrows)`` of a row-slab call as ints, ``nrows`` defaulting to the rest of the matrix: inside ``[0, m)``,
+        or the library's own ``ValueError``."""
+        row0 = int(row0)
+        nrows = self.m - row0 if nrows is None else int(nrows)
+        if row0 < 0 or nrows < 0 or row0 + nrows > self.m:
+            raise ValueError(f"rows [{row0}, {row0} + {nrows}) are not inside [0, {self.m})")
+        return row0, nrows
+
     def predict_rows(self, row0=0, nrows=None, clip_theta=True, threshold=None, out=None):
         """Theta for rows ``[row0, row0 + nrows)`` and all n columns (``nbmf_predict_rows``): a float64 ``(nrows, n)``
         array, or with a ``threshold`` the bool array ``Theta > threshold``, compared on the device (one byte per entry
         comes back).  ``out``, if given, is written and returned: shape ``(nrows, n)``, float64 (bool or uint8 with a
         threshold), unit stride along a row and any row stride of at least n elements -- a slice of a wider array is fine,
         and nothing outside the slice is touched."""
-        row0 = int(row0)
-        nrows = self.m - row0 if nrows is None else int(nrows)
+        row0, nrows = self._rows(row0, nrows)
         byte_kind = threshold is not None
         if out is None:
-            out = np.empty((max(nrows, 0), self.n), dtype=np.bool_ if byte_kind else np.float64)
-        else:
-            ok_types = (np.bool_, np.uint8) if byte_kind else (np.float64,)
-            if not isinstance(out, np.ndarray) or out.dtype not in ok_types or out.shape != (nrows, self.n):
-                raise ValueError(f"out must be a {ok_types[0].__name__} array of shape ({nrows}, {self.n})")
-            if out.size and (out.strides[1] != out.itemsize or (nrows > 1 and (
-                    out.strides[0] < self.n * out.itemsize or out.strides[0] % out.itemsize))):
-                raise ValueError("out must have unit stride along a row and a row stride of at least n elements")
-        ld = out.strides[0] // out.itemsize if out.size and out.shape[0] > 1 else self.n
+            out = np.empty((nrows, self.n), dtype=np.bool_ if byte_kind else np.float64)
+        elif not isinstance(out, np.ndarray):
+            raise ValueError(f"out must be a NumPy array: it is written in place (got {type(out).__name__})")
+        ld = row_array(out, nrows, self.n, "out", BYTE_KINDS if byte_kind else (np.float64,))[2]
         _check(self._lib.nbmf_predict_rows(self._h, row0, nrows, int(bool(clip_theta)), PREDICT_U8 if byte_kind else PREDICT_F64,
-                                           float(threshold) if byte_kind else 0.0, out.ctypes.data_as(c_void_p), int(ld)))
+                                           float(threshold) if byte_kind else 0.0, out.ctypes.data_as(c_void_p), ld))
         return out
 
     def top_n(self, top, row0=0, nrows=None, exclude=None, clip_theta=True, return_scores=True):
@@ -512,13 +507,10 @@ class Context:
         least n: a slice of a wider array is fine).  A NaN Theta is never returned.  A row with fewer than ``top`` columns
         left ends in column -1 / score NaN.  Only ``top`` entries per row come back from the device, not n."""
         top = top_n_count(top)
-        row0 = int(row0)
-        nrows = self.m - row0 if nrows is None else int(nrows)
-        if row0 < 0 or nrows < 0 or row0 + nrows > self.m:
-            raise ValueError(f"rows [{row0}, {row0} + {nrows}) are not inside [0, {self.m})")
+        row0, nrows = self._rows(row0, nrows)
         xptr, ldx = None, 0
         if exclude is not None:
-            exclude, ldx = exclude_bytes(exclude, nrows, self.n)
+            exclude, _, ldx = row_array(exclude, nrows, self.n, "exclude", BYTE_KINDS)
             xptr = exclude.ctypes.data_as(c_void_p)
         cols = np.empty((nrows, top), dtype=np.int64)
         scores = np.empty((nrows, top), dtype=np.float64) if return_scores else None
@@ -535,19 +527,16 @@ class Context:
         + eps)``).  ``mask``: bool / uint8 of the same shape, nonzero = observed; None: every entry.  Both may be slices of
         wider arrays (unit stride along a row); nothing is copied on the host.  Theta is bit for bit what
         :meth:`predict_rows` returns.  Only ``nrows + n`` sums and counts come back from the device."""
-        row0 = int(row0)
-        nrows = self.m - row0 if nrows is None else int(nrows)
-        if row0 < 0 or nrows < 0 or row0 + nrows > self.m:
-            raise ValueError(f"rows [{row0}, {row0} + {nrows}) are not inside [0, {self.m})")
+        row0, nrows = self._rows(row0, nrows)
         if not rows and not cols:
             raise ValueError("nothing requested: rows and cols are both false")
         eps = float(eps)
         if not eps >= 0.0:
             raise ValueError(f"eps must be >= 0 (got {eps})")
-        x, x_kind, ldx = score_panel(x, nrows, self.n, "x")
+        x, x_kind, ldx = row_array(x, nrows, self.n, "x", ANY_KINDS)
         mptr, ldm = None, 0
         if mask is not None:
-            mask, _, ldm = score_panel(mask, nrows, self.n, "mask", byte_only=True)
+            mask, _, ldm = row_array(mask, nrows, self.n, "mask", BYTE_KINDS)
             mptr = mask.ctypes.data_as(c_void_p)
         row_ll = np.empty(nrows, dtype=np.float64) if rows else None
         row_obs = np.empty(nrows, dtype=np.int64) if rows else None

@@ -5,6 +5,8 @@ simplex touch-up stay on the host exactly as the reference orders them.
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 
 from . import _hip
@@ -253,16 +255,24 @@ def device_score(X, H, mask=None, n_iter=50, device=0):
     return float(ll / n_obs)
 
 
+@contextlib.contextmanager
+def _factors_only(W, H, device):
+    """``(ctx, m, n)``: a context that holds the factors ``W`` (m, k) and ``H`` (k, n) and no data -- what the functions
+    that read Theta back run on."""
+    m, k = W.shape
+    n = H.shape[1]
+    with _hip.Context(m, n, k, device=device) as ctx:
+        ctx.set_factors(np.ascontiguousarray(W.T), H)
+        yield ctx, m, n
+
+
 def device_predict(W, H, rows=None, cols=None, threshold=None, device=0):
     """Theta = ``W @ H`` clipped to [0, 1] (``NBMFMM.inverse_transform``, src/nbmf_mm/_base.py:201-210) on the GPU, for
     ``W`` (rows, k) and ``H`` (k, features) as the estimator holds them (user layout in both orientations: the solver
     has un-transposed them).  With ``rows`` / ``cols`` (already validated: ``_hip.index_pairs``) the values at those
     pairs; otherwise the dense matrix, as float64 or, with a ``threshold``, as the bool matrix ``Theta > threshold``
     compared on the device.  The context holds factors only: no data is uploaded."""
-    m, k = W.shape
-    n = H.shape[1]
-    with _hip.Context(m, n, k, device=device) as ctx:
-        ctx.set_factors(np.ascontiguousarray(W.T), H)
+    with _factors_only(W, H, device) as (ctx, m, n):
         if rows is not None:
             return ctx.predict_at(rows, cols, clip_theta=True)
         return ctx.predict_rows(0, m, clip_theta=True, threshold=threshold)
@@ -278,13 +288,9 @@ def device_top_n(W, H, top, exclude=None, device=0):
     ``exclude`` already validated (``_hip.top_n_count``; shape ``(rows, features)``, dense of a bool / integer / floating
     dtype or scipy-sparse, nonzero = skip).  ``exclude`` is made dense one row block at a time, so the host never holds
     more than ``TOP_N_EXCLUDE_BLOCK_BYTES`` of it beyond what the caller passed.  Factors only: no data is uploaded."""
-    m, k = W.shape
-    n = H.shape[1]
-    sparse = hasattr(exclude, "toarray")
-    if sparse:
+    if hasattr(exclude, "toarray"):
         exclude = exclude.tocsr()
-    with _hip.Context(m, n, k, device=device) as ctx:
-        ctx.set_factors(np.ascontiguousarray(W.T), H)
+    with _factors_only(W, H, device) as (ctx, m, n):
         if exclude is None:
             return ctx.top_n(top, 0, m, clip_theta=True)
         cols = np.empty((m, top), dtype=np.int64)
@@ -292,12 +298,7 @@ def device_top_n(W, H, top, exclude=None, device=0):
         block = max(1, min(m, TOP_N_EXCLUDE_BLOCK_BYTES // max(n, 1)))
         for r0 in range(0, m, block):
             nr = min(block, m - r0)
-            x = exclude[r0:r0 + nr]
-            if sparse:
-                x = (x != 0).toarray()                     # (a bool block, whatever the stored dtype)
-            x = np.asarray(x)
-            if x.dtype != np.bool_ and x.dtype != np.uint8:
-                x = x != 0
+            x = _row_block(exclude, r0, nr, True)
             cols[r0:r0 + nr], scores[r0:r0 + nr] = ctx.top_n(top, r0, nr, exclude=x, clip_theta=True)
         return cols, scores
 
@@ -306,10 +307,11 @@ def device_top_n(W, H, top, exclude=None, device=0):
 SCORE_SAMPLES_BLOCK_BYTES = 64 << 20
 
 
-def _score_block(A, r0, nr, is_mask):
-    """Rows ``[r0, r0 + nr)`` of the data or the mask as ``Context.score_rows`` takes them.  A bool / uint8 block is
-    passed as it is; a mask of another dtype as ``!= 0``; other data as uint8 when the block is exactly {0, 1}, else as
-    float64.  A sparse block is made dense first; a block that is not laid out row after row is copied."""
+def _row_block(A, r0, nr, is_mask):
+    """Rows ``[r0, r0 + nr)`` of the data of ``Context.score_rows``, or of a mask (its ``mask``, the ``exclude`` of
+    ``Context.top_n``), as the context takes them.  A bool / uint8 block is passed as it is; a mask of another dtype as
+    ``!= 0``; other data as uint8 when the block is exactly {0, 1}, else as float64.  A sparse block is made dense first
+    (a mask as a bool block, whatever the stored dtype); a block that is not laid out row after row is copied."""
     a = A[r0:r0 + nr]
     if hasattr(a, "toarray"):
         a = (a != 0).toarray() if is_mask else a.toarray()
@@ -336,8 +338,6 @@ def device_score_samples(W, H, X, mask=None, axis=0, device=0):
     data goes as uint8 where the block is exactly {0, 1} and as float64 otherwise.  A row's result does not depend on the
     blocks.  For ``axis=1`` the blocks' sums and counts are added on the host in ascending order: feature scores of
     block-streamed input equal the one-call result to rounding, not bit for bit."""
-    m, k = W.shape
-    n = H.shape[1]
     byte = lambda a: a is None or (not hasattr(a, "toarray") and a.dtype in (np.bool_, np.uint8))   # noqa: E731
     if hasattr(X, "toarray"):
         X = X.tocsr()
@@ -345,15 +345,14 @@ def device_score_samples(W, H, X, mask=None, axis=0, device=0):
         X = np.asarray(X)
     if mask is not None:
         mask = mask.tocsr() if hasattr(mask, "toarray") else np.asarray(mask)
-    block = m if byte(X) and byte(mask) else max(16, SCORE_SAMPLES_BLOCK_BYTES // (8 * max(n, 1)) // 16 * 16)
-    sums = np.zeros(n if axis else m, dtype=np.float64)
-    counts = np.zeros(n if axis else m, dtype=np.int64)
-    with _hip.Context(m, n, k, device=device) as ctx:
-        ctx.set_factors(np.ascontiguousarray(W.T), H)
+    with _factors_only(W, H, device) as (ctx, m, n):
+        block = m if byte(X) and byte(mask) else max(16, SCORE_SAMPLES_BLOCK_BYTES // (8 * max(n, 1)) // 16 * 16)
+        sums = np.zeros(n if axis else m, dtype=np.float64)
+        counts = np.zeros(n if axis else m, dtype=np.int64)
         for r0 in range(0, m, max(block, 1)):
             nr = min(block, m - r0)
-            x = _score_block(X, r0, nr, False)
-            mk = None if mask is None else _score_block(mask, r0, nr, True)
+            x = _row_block(X, r0, nr, False)
+            mk = None if mask is None else _row_block(mask, r0, nr, True)
             rl, ro, cl, co = ctx.score_rows(x, mk, r0, nr, clip_theta=True, eps=1e-8, rows=not axis, cols=bool(axis))
             if axis:
                 sums += cl

@@ -2477,8 +2477,9 @@ int one_shot(nbmf_ctx* c, bool with_prior, int strict, int clip, bool collect_ti
 // (also the single-launch engine's end-of-run guard: small_guard)
 int loss_by_launches(nbmf_ctx* c, double* loss) { return one_shot(c, /*with_prior=*/true, 0, 0, /*collect_timing=*/true, loss); }
 
-// Staging of one predict call (nbmf_predict_at / nbmf_predict_rows), from the pool: given back when the call returns, on
-// every path, after the stream has drained (a pooled block may be handed to the next caller at once).
+// ---- shared by the four entry points that read Theta back: nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows
+// (DESIGN.md 4.6).  Staging of one such call, from the pool: given back when the call returns, on every path, after the
+// stream has drained (a pooled block may be handed to the next caller at once).
 struct PredictStage {
   hipStream_t stream;
   std::vector<void*> blocks;
@@ -2495,12 +2496,73 @@ struct PredictStage {
   }
 };
 
-// The checks both predict entry points share, in the order the header gives them: factors, not data (so not ready()).
+// The checks all four share, in the order the header gives them: factors, not data (so not ready()).
 int predict_ready(nbmf_ctx* c) {
   if (!c) return fail(NBMF_ERR_ARG, "null context");
   if (!c->have_factors) return fail(NBMF_ERR_STATE, "no factors on the device");
   if (is_sharded(c)) return fail(NBMF_ERR_STATE, "prediction runs on an unsharded context (nbmf_comm_detach first)");
   return NBMF_OK;
+}
+
+int check_rows(nbmf_ctx* c, int64_t row0, int64_t nrows) {   // the three row-slab entry points: all but nbmf_predict_at
+  if (nrows < 0 || row0 < 0 || row0 > c->m || nrows > c->m - row0)
+    return fail(NBMF_ERR_ARG, "rows [%lld, %lld + %lld) are not inside [0, %lld)", (long long)row0, (long long)row0, (long long)nrows,
+                (long long)c->m);
+  return NBMF_OK;
+}
+
+// rows x width bytes between a caller's rows and a staging panel: one flat copy where both sides are dense, else the 2D
+// copy.  Only `width` bytes of a row are touched on either side, whatever its pitch: nothing of a caller's array beyond
+// column n - 1 (slot top - 1) is read or written.
+hipError_t copy_rows(void* dst, size_t dst_pitch, const void* src, size_t src_pitch, size_t width, size_t rows, hipMemcpyKind kind,
+                     hipStream_t stream) {
+  if (dst_pitch == width && src_pitch == width) return hipMemcpyAsync(dst, src, rows * width, kind, stream);
+  return hipMemcpy2DAsync(dst, dst_pitch, src, src_pitch, width, rows, kind, stream);
+}
+
+// How a row-slab call walks its rows [row0, end), in panels that share one staging and end in a stream synchronise each:
+//   for (long long p0 = row0, pn; p0 < pl.end; p0 += pn) { pn = pl.rows_at(p0); ... }
+// A panel is NBMF_PREDICT_PANEL_ROWS rows high, or else what 256 MiB of staging hold at row_bytes per panel row, rounded
+// down to a multiple of 16 with a floor of 16.  With align16 the height is rounded up to 16 and the first panel is cut
+// short by row0 % 16, so that every later panel starts on the absolute 16-row grid: a 16-row block of the product kernels
+// never straddles two panels (nbmf_score_rows' column sums rely on it: DESIGN.md 4.8).
+struct RowPanels {
+  long long ldp;          // round_up(n, 4) (<= nA): a staged panel's leading dimension -- the kernels move 4 entries at a time
+  long long col_groups;   // gridDim.y of a product kernel: PR_WAVES strips of PR_STRIP columns per workgroup
+  long long row0, end, panel;
+  bool align16;
+  long long stage_rows() const { return std::min(panel, end - row0); }   // (no panel holds more rows than this)
+  long long rows_at(long long p0) const { return std::min(align16 ? panel - p0 % 16 : panel, end - p0); }
+  static long long blocks(long long p0, long long pn) { return (p0 + pn + 15) / 16 - p0 / 16; }
+  dim3 grid(long long p0, long long pn) const { return dim3((unsigned)blocks(p0, pn), (unsigned)col_groups); }
+};
+inline long long panel_ld(const nbmf_ctx* c) { return round_up(c->n, 4); }
+
+int plan_row_panels(nbmf_ctx* c, const char* who, int64_t row0, int64_t nrows, size_t row_bytes, bool align16, RowPanels* pl) {
+  const long long col_groups = (c->nA + PR_WAVES * PR_STRIP - 1) / (PR_WAVES * PR_STRIP);
+  if (col_groups > 65535) return fail(NBMF_ERR_ARG, "n = %lld is beyond what %s launches", (long long)c->n, who);
+  const long long dflt = std::max<long long>(16, (long long)((256ull << 20) / row_bytes) / 16 * 16);
+  const long long panel = std::max<long long>(1, env_int("NBMF_PREDICT_PANEL_ROWS", dflt));
+  *pl = RowPanels{panel_ld(c), col_groups, row0, row0 + nrows, align16 ? (long long)round_up(panel, 16) : panel, align16};
+  return NBMF_OK;
+}
+
+// Rows [p0, p0 + pn) of Theta into the staging panel of leading dimension pl.ldp (nbmf_predict_rows, nbmf_top_n).
+hipError_t launch_theta_panel(nbmf_ctx* c, const RowPanels& pl, long long p0, long long pn, int out_kind, int clip, double threshold,
+                              void* panel_d) {
+  hipLaunchKernelGGL(out_kind == NBMF_PREDICT_U8 ? predict_rows_kernel<1> : predict_rows_kernel<0>, pl.grid(p0, pn),
+                     dim3(PR_WAVES * 64), 0, c->stream, (const double*)c->Wn, (const double*)c->Hn, c->k, (long long)c->mA,
+                     (long long)c->nA, p0, pn, pl.ldp, clip != 0 ? 1 : 0, threshold, panel_d);
+  return hipGetLastError();
+}
+
+// The same rows of Theta scored against the staged data and mask panels (nbmf_score_rows).
+hipError_t launch_score_panel(nbmf_ctx* c, const RowPanels& pl, long long p0, long long pn, int x_kind, int clip, double eps,
+                              const void* x_d, const unsigned char* m_d, double* rpart_d, int* rcnt_d, double* cpart_d, int* ccnt_d) {
+  hipLaunchKernelGGL(x_kind == NBMF_DATA_F64 ? score_rows_kernel<1> : score_rows_kernel<0>, pl.grid(p0, pn), dim3(PR_WAVES * 64), 0,
+                     c->stream, (const double*)c->Wn, (const double*)c->Hn, c->k, (long long)c->mA, (long long)c->nA,
+                     (long long)c->n, p0, pn, pl.ldp, clip != 0 ? 1 : 0, eps, x_d, m_d, rpart_d, rcnt_d, cpart_d, ccnt_d);
+  return hipGetLastError();
 }
 
 }  // namespace
@@ -3299,9 +3361,7 @@ int nbmf_predict_at(nbmf_ctx* c, const int64_t* rows, const int64_t* cols, int64
 int nbmf_predict_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, int out_kind, double threshold, void* out,
                       int64_t ldout) {
   if (int rc = predict_ready(c)) return rc;
-  if (nrows < 0 || row0 < 0 || row0 > c->m || nrows > c->m - row0)
-    return fail(NBMF_ERR_ARG, "rows [%lld, %lld + %lld) are not inside [0, %lld)", (long long)row0, (long long)row0, (long long)nrows,
-                (long long)c->m);
+  if (int rc = check_rows(c, row0, nrows)) return rc;
   if (ldout < c->n) return fail(NBMF_ERR_ARG, "ldout %lld is less than n = %lld", (long long)ldout, (long long)c->n);
   if (out_kind != NBMF_PREDICT_F64 && out_kind != NBMF_PREDICT_U8) return fail(NBMF_ERR_ARG, "unknown out_kind %d", out_kind);
   if (out_kind == NBMF_PREDICT_U8 && threshold != threshold) return fail(NBMF_ERR_ARG, "threshold is NaN");
@@ -3309,30 +3369,16 @@ int nbmf_predict_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, 
   if (!out) return fail(NBMF_ERR_ARG, "null output");
   if (int rc = set_device(c)) return rc;
   const size_t elt = out_kind == NBMF_PREDICT_U8 ? 1 : sizeof(double);
-  const long long ldd = round_up(c->n, 4);   // (<= nA) the panel's leading dimension: the kernel stores 4 entries at a time
-  const long long dflt = std::max<long long>(16, (long long)((256ull << 20) / ((size_t)ldd * elt)) / 16 * 16);
-  const long long panel = std::min<long long>(nrows, std::max<long long>(1, env_int("NBMF_PREDICT_PANEL_ROWS", dflt)));
-  const long long col_groups = (c->nA + PR_WAVES * PR_STRIP - 1) / (PR_WAVES * PR_STRIP);
-  if (col_groups > 65535) return fail(NBMF_ERR_ARG, "n = %lld is beyond what nbmf_predict_rows launches", (long long)c->n);
+  RowPanels pl;
+  if (int rc = plan_row_panels(c, "nbmf_predict_rows", row0, nrows, (size_t)panel_ld(c) * elt, false, &pl)) return rc;
   PredictStage st{c->stream, {}};
   char* panel_d = nullptr;
-  HIPCHK(st.get(&panel_d, (size_t)panel * ldd * elt));
-  for (long long p0 = row0; p0 < row0 + nrows; p0 += panel) {
-    const long long pn = std::min(panel, (long long)(row0 + nrows) - p0);
-    const dim3 grid((unsigned)((p0 + pn + 15) / 16 - p0 / 16), (unsigned)col_groups);
-    if (out_kind == NBMF_PREDICT_U8)
-      hipLaunchKernelGGL(predict_rows_kernel<1>, grid, dim3(PR_WAVES * 64), 0, c->stream, (const double*)c->Wn, (const double*)c->Hn,
-                         c->k, (long long)c->mA, (long long)c->nA, p0, pn, ldd, clip_theta != 0 ? 1 : 0, threshold, (void*)panel_d);
-    else
-      hipLaunchKernelGGL(predict_rows_kernel<0>, grid, dim3(PR_WAVES * 64), 0, c->stream, (const double*)c->Wn, (const double*)c->Hn,
-                         c->k, (long long)c->mA, (long long)c->nA, p0, pn, ldd, clip_theta != 0 ? 1 : 0, threshold, (void*)panel_d);
-    HIPCHK(hipGetLastError());
-    char* dst = (char*)out + (size_t)(p0 - row0) * (size_t)ldout * elt;
-    if (ldout == c->n && ldd == c->n)   // (nothing of `out` beyond column n - 1 is ever written)
-      HIPCHK(hipMemcpyAsync(dst, panel_d, (size_t)pn * ldd * elt, hipMemcpyDeviceToHost, c->stream));
-    else
-      HIPCHK(hipMemcpy2DAsync(dst, (size_t)ldout * elt, panel_d, (size_t)ldd * elt, (size_t)c->n * elt, (size_t)pn,
-                              hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(st.get(&panel_d, (size_t)pl.stage_rows() * pl.ldp * elt));
+  for (long long p0 = row0, pn; p0 < pl.end; p0 += pn) {
+    pn = pl.rows_at(p0);
+    HIPCHK(launch_theta_panel(c, pl, p0, pn, out_kind, clip_theta, threshold, panel_d));
+    HIPCHK(copy_rows((char*)out + (size_t)(p0 - row0) * ldout * elt, ldout * elt, panel_d, pl.ldp * elt, c->n * elt, pn,
+                     hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
   }
   return NBMF_OK;
@@ -3345,73 +3391,49 @@ int nbmf_top_n(nbmf_ctx* c, int64_t row0, int64_t nrows, int top, int clip_theta
                int64_t* out_cols, double* out_scores, int64_t ldout) {
   if (int rc = predict_ready(c)) return rc;
   if (top < 1 || top > NBMF_TOP_N_MAX) return fail(NBMF_ERR_ARG, "top must be in [1, %d] (got %d)", NBMF_TOP_N_MAX, top);
-  if (nrows < 0 || row0 < 0 || row0 > c->m || nrows > c->m - row0)
-    return fail(NBMF_ERR_ARG, "rows [%lld, %lld + %lld) are not inside [0, %lld)", (long long)row0, (long long)row0, (long long)nrows,
-                (long long)c->m);
+  if (int rc = check_rows(c, row0, nrows)) return rc;
   if (ldout < top) return fail(NBMF_ERR_ARG, "ldout %lld is less than top = %d", (long long)ldout, top);
   if (exclude && ldx < c->n) return fail(NBMF_ERR_ARG, "ldx %lld is less than n = %lld", (long long)ldx, (long long)c->n);
   if (nrows == 0) return NBMF_OK;
   if (!out_cols) return fail(NBMF_ERR_ARG, "null output");
   if (int rc = set_device(c)) return rc;
   static_assert(NBMF_TOP_N_MAX == TN_MAX, "the kernel's entry list holds NBMF_TOP_N_MAX slots");
-  const long long n = c->n, ldd = round_up(n, 4);   // (the panel of nbmf_predict_rows, float64)
-  const long long dflt = std::max<long long>(16, (long long)((256ull << 20) / ((size_t)ldd * sizeof(double))) / 16 * 16);
-  const long long panel = std::min<long long>(nrows, std::max<long long>(1, env_int("NBMF_PREDICT_PANEL_ROWS", dflt)));
-  const long long col_groups = (c->nA + PR_WAVES * PR_STRIP - 1) / (PR_WAVES * PR_STRIP);
-  if (col_groups > 65535) return fail(NBMF_ERR_ARG, "n = %lld is beyond what nbmf_top_n launches", (long long)n);
+  const long long n = c->n;
+  RowPanels pl;   // (the panel of nbmf_predict_rows, float64)
+  if (int rc = plan_row_panels(c, "nbmf_top_n", row0, nrows, (size_t)panel_ld(c) * sizeof(double), false, &pl)) return rc;
+  const size_t rows = (size_t)pl.stage_rows(), w64 = sizeof(int64_t) * (size_t)top, pitch = sizeof(int64_t) * (size_t)ldout;
   PredictStage st{c->stream, {}};
   double *panel_d = nullptr, *scores_d = nullptr;
   long long* cols_d = nullptr;
   unsigned char* ex_d = nullptr;
-  HIPCHK(st.get(&panel_d, sizeof(double) * (size_t)panel * ldd));
-  HIPCHK(st.get(&cols_d, sizeof(long long) * (size_t)panel * top));
-  if (out_scores) HIPCHK(st.get(&scores_d, sizeof(double) * (size_t)panel * top));
-  if (exclude) HIPCHK(st.get(&ex_d, (size_t)panel * n));
-  for (long long p0 = row0; p0 < row0 + nrows; p0 += panel) {
-    const long long pn = std::min(panel, (long long)(row0 + nrows) - p0);
+  HIPCHK(st.get(&panel_d, sizeof(double) * rows * pl.ldp));
+  HIPCHK(st.get(&cols_d, rows * w64));
+  if (out_scores) HIPCHK(st.get(&scores_d, rows * w64));
+  if (exclude) HIPCHK(st.get(&ex_d, rows * n));
+  for (long long p0 = row0, pn; p0 < pl.end; p0 += pn) {
+    pn = pl.rows_at(p0);
     const size_t done = (size_t)(p0 - row0);
-    if (exclude) {   // (n bytes of every row: nothing of the caller's array beyond column n - 1 is read)
-      const uint8_t* src = exclude + done * (size_t)ldx;
-      if (ldx == n)
-        HIPCHK(hipMemcpyAsync(ex_d, src, (size_t)pn * n, hipMemcpyHostToDevice, c->stream));
-      else
-        HIPCHK(hipMemcpy2DAsync(ex_d, (size_t)n, src, (size_t)ldx, (size_t)n, (size_t)pn, hipMemcpyHostToDevice, c->stream));
-    }
-    const dim3 grid((unsigned)((p0 + pn + 15) / 16 - p0 / 16), (unsigned)col_groups);
-    hipLaunchKernelGGL(predict_rows_kernel<0>, grid, dim3(PR_WAVES * 64), 0, c->stream, (const double*)c->Wn, (const double*)c->Hn,
-                       c->k, (long long)c->mA, (long long)c->nA, p0, pn, ldd, clip_theta != 0 ? 1 : 0, 0.0, (void*)panel_d);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(top_n_kernel, dim3((unsigned)pn), dim3(TN_THREADS), 0, c->stream, (const double*)panel_d, ldd, n,
+    if (exclude) HIPCHK(copy_rows(ex_d, n, exclude + done * ldx, ldx, n, pn, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_theta_panel(c, pl, p0, pn, NBMF_PREDICT_F64, clip_theta, 0.0, panel_d));
+    hipLaunchKernelGGL(top_n_kernel, dim3((unsigned)pn), dim3(TN_THREADS), 0, c->stream, (const double*)panel_d, pl.ldp, n,
                        (const unsigned char*)ex_d, n, top, cols_d, scores_d);
     HIPCHK(hipGetLastError());
-    const size_t w64 = sizeof(int64_t) * (size_t)top;   // (nothing of an output row beyond slot top - 1 is written)
-    if (ldout == top) {
-      HIPCHK(hipMemcpyAsync(out_cols + done * top, cols_d, (size_t)pn * w64, hipMemcpyDeviceToHost, c->stream));
-      if (out_scores) HIPCHK(hipMemcpyAsync(out_scores + done * top, scores_d, (size_t)pn * w64, hipMemcpyDeviceToHost, c->stream));
-    } else {
-      const size_t pitch = sizeof(int64_t) * (size_t)ldout;
-      HIPCHK(hipMemcpy2DAsync(out_cols + done * (size_t)ldout, pitch, cols_d, w64, w64, (size_t)pn, hipMemcpyDeviceToHost, c->stream));
-      if (out_scores)
-        HIPCHK(hipMemcpy2DAsync(out_scores + done * (size_t)ldout, pitch, scores_d, w64, w64, (size_t)pn, hipMemcpyDeviceToHost,
-                                c->stream));
-    }
+    HIPCHK(copy_rows(out_cols + done * ldout, pitch, cols_d, w64, w64, pn, hipMemcpyDeviceToHost, c->stream));
+    if (out_scores) HIPCHK(copy_rows(out_scores + done * ldout, pitch, scores_d, w64, w64, pn, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
   }
   return NBMF_OK;
 }
 
 // ---- Theta judged against data: log-likelihood per row and per column (nbmf_score_kernels.inc) -------------
-// Per panel: the caller's data and mask rows up into staging panels of leading dimension round_up(n, 4) (n bytes or
-// doubles of every row: nothing beyond column n - 1 is read), the fused product-and-score kernel, then the finishing
-// steps -- the strips of a row in ascending order, the 16-row blocks of a column in ascending order onto accumulators that
-// stay on the device for the whole call.  Panels after the first start on a multiple of 16 of the absolute row index, so a
-// 16-row block never straddles two panels and a column's chain of additions is the same whatever the panel height.
+// Per panel: the caller's data and mask rows up into staging panels (copy_rows), the fused product-and-score kernel, then
+// the finishing steps -- the strips of a row in ascending order, the 16-row blocks of a column in ascending order onto
+// accumulators that stay on the device for the whole call.  The panels are 16-aligned (RowPanels), so a 16-row block never
+// straddles two of them and a column's chain of additions is the same whatever the panel height.
 int nbmf_score_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, double eps, const void* x, int x_kind, int64_t ldx,
                     const uint8_t* mask, int64_t ldmask, double* row_ll, int64_t* row_obs, double* col_ll, int64_t* col_obs) {
   if (int rc = predict_ready(c)) return rc;
-  if (nrows < 0 || row0 < 0 || row0 > c->m || nrows > c->m - row0)
-    return fail(NBMF_ERR_ARG, "rows [%lld, %lld + %lld) are not inside [0, %lld)", (long long)row0, (long long)row0, (long long)nrows,
-                (long long)c->m);
+  if (int rc = check_rows(c, row0, nrows)) return rc;
   if (x_kind != NBMF_DATA_U8 && x_kind != NBMF_DATA_F64) return fail(NBMF_ERR_ARG, "unknown x_kind %d", x_kind);
   if (ldx < c->n) return fail(NBMF_ERR_ARG, "ldx %lld is less than n = %lld", (long long)ldx, (long long)c->n);
   if (mask && ldmask < c->n) return fail(NBMF_ERR_ARG, "ldmask %lld is less than n = %lld", (long long)ldmask, (long long)c->n);
@@ -3427,17 +3449,14 @@ int nbmf_score_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, do
   if (int rc = set_device(c)) return rc;
   const bool want_rows = row_ll || row_obs, want_cols = col_ll || col_obs;
   const size_t elt = x_kind == NBMF_DATA_F64 ? sizeof(double) : 1;
-  const long long ldp = round_up(n, 4);                        // (<= nA) the staged panels' leading dimension
+  const long long ldp = panel_ld(c);
   const long long strips = (n + PR_STRIP - 1) / PR_STRIP;      // the strips that hold a real column
-  const long long col_groups = (c->nA + PR_WAVES * PR_STRIP - 1) / (PR_WAVES * PR_STRIP);
-  if (col_groups > 65535) return fail(NBMF_ERR_ARG, "n = %lld is beyond what nbmf_score_rows launches", (long long)n);
   // the budget of nbmf_predict_rows over everything a panel row stages: data, mask, its strip partials, its share of a block's
   const size_t per_row = (size_t)ldp * (elt + (mask ? 1 : 0)) + (want_rows ? (size_t)strips * 12 + 16 : 0) +
                          (want_cols ? ((size_t)ldp * 12 + 15) / 16 : 0);
-  const long long dflt = std::max<long long>(16, (long long)((256ull << 20) / per_row) / 16 * 16);
-  const long long panel = round_up(std::max<long long>(1, env_int("NBMF_PREDICT_PANEL_ROWS", dflt)), 16);
-  const long long stage_rows = std::min<long long>(panel, nrows);   // (no panel holds more rows than either)
-  const long long max_blocks = stage_rows / 16 + 2;                 // (... nor touches more 16-row blocks than this)
+  RowPanels pl;
+  if (int rc = plan_row_panels(c, "nbmf_score_rows", row0, nrows, per_row, true, &pl)) return rc;
+  const long long stage_rows = pl.stage_rows(), max_blocks = stage_rows / 16 + 2;   // (no panel touches more 16-row blocks)
   PredictStage st{c->stream, {}};
   char* x_d = nullptr;
   unsigned char* m_d = nullptr;
@@ -3460,34 +3479,12 @@ int nbmf_score_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, do
     HIPCHK(hipMemsetAsync(col_ll_d, 0, sizeof(double) * (size_t)n, c->stream));
     HIPCHK(hipMemsetAsync(col_obs_d, 0, sizeof(long long) * (size_t)n, c->stream));
   }
-  const long long end = row0 + nrows;
-  for (long long p0 = row0; p0 < end;) {
-    const long long pn = std::min(panel - p0 % 16, end - p0);   // (p0 + pn is a multiple of 16, or the end)
+  for (long long p0 = row0, pn; p0 < pl.end; p0 += pn) {
+    pn = pl.rows_at(p0);   // (p0 + pn is a multiple of 16, or the end)
     const size_t done = (size_t)(p0 - row0);
-    const char* xsrc = (const char*)x + done * (size_t)ldx * elt;
-    if (ldx == n && ldp == n)
-      HIPCHK(hipMemcpyAsync(x_d, xsrc, (size_t)pn * n * elt, hipMemcpyHostToDevice, c->stream));
-    else
-      HIPCHK(hipMemcpy2DAsync(x_d, (size_t)ldp * elt, xsrc, (size_t)ldx * elt, (size_t)n * elt, (size_t)pn, hipMemcpyHostToDevice,
-                              c->stream));
-    if (mask) {
-      const uint8_t* msrc = mask + done * (size_t)ldmask;
-      if (ldmask == n && ldp == n)
-        HIPCHK(hipMemcpyAsync(m_d, msrc, (size_t)pn * n, hipMemcpyHostToDevice, c->stream));
-      else
-        HIPCHK(hipMemcpy2DAsync(m_d, (size_t)ldp, msrc, (size_t)ldmask, (size_t)n, (size_t)pn, hipMemcpyHostToDevice, c->stream));
-    }
-    const long long blocks = (p0 + pn + 15) / 16 - p0 / 16;   // (<= max_blocks)
-    const dim3 grid((unsigned)blocks, (unsigned)col_groups);
-    if (x_kind == NBMF_DATA_F64)
-      hipLaunchKernelGGL(score_rows_kernel<1>, grid, dim3(PR_WAVES * 64), 0, c->stream, (const double*)c->Wn, (const double*)c->Hn,
-                         c->k, (long long)c->mA, (long long)c->nA, n, p0, pn, ldp, clip_theta != 0 ? 1 : 0, eps, (const void*)x_d,
-                         (const unsigned char*)m_d, rpart_d, rcnt_d, cpart_d, ccnt_d);
-    else
-      hipLaunchKernelGGL(score_rows_kernel<0>, grid, dim3(PR_WAVES * 64), 0, c->stream, (const double*)c->Wn, (const double*)c->Hn,
-                         c->k, (long long)c->mA, (long long)c->nA, n, p0, pn, ldp, clip_theta != 0 ? 1 : 0, eps, (const void*)x_d,
-                         (const unsigned char*)m_d, rpart_d, rcnt_d, cpart_d, ccnt_d);
-    HIPCHK(hipGetLastError());
+    HIPCHK(copy_rows(x_d, ldp * elt, (const char*)x + done * ldx * elt, ldx * elt, n * elt, pn, hipMemcpyHostToDevice, c->stream));
+    if (mask) HIPCHK(copy_rows(m_d, ldp, mask + done * ldmask, ldmask, n, pn, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_score_panel(c, pl, p0, pn, x_kind, clip_theta, eps, x_d, m_d, rpart_d, rcnt_d, cpart_d, ccnt_d));
     if (want_rows) {
       hipLaunchKernelGGL(score_rows_finish_kernel, dim3((unsigned)((pn + 255) / 256)), dim3(256), 0, c->stream,
                          (const double*)rpart_d, (const int*)rcnt_d, pn, strips, row_ll_d, row_obs_d);
@@ -3498,11 +3495,10 @@ int nbmf_score_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, do
     }
     if (want_cols) {
       hipLaunchKernelGGL(score_cols_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                         (const double*)cpart_d, (const int*)ccnt_d, blocks, ldp, n, col_ll_d, col_obs_d);
+                         (const double*)cpart_d, (const int*)ccnt_d, RowPanels::blocks(p0, pn), ldp, n, col_ll_d, col_obs_d);
       HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
-    p0 += pn;
   }
   if (col_ll) HIPCHK(hipMemcpyAsync(col_ll, col_ll_d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   if (col_obs) HIPCHK(hipMemcpyAsync(col_obs, col_obs_d, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));

@@ -1,9 +1,10 @@
 // nbmf_predict_kernels.inc -- Theta = W^T H handed back to the caller (nbmf_predict_at, nbmf_predict_rows; DESIGN.md 4.6)
-// and ranked on the device (nbmf_top_n: top_n_kernel at the end of this file; DESIGN.md 4.7).
-// Included by nbmf_hip.hip after the other kernel files.  Both product kernels read the natural padded factor images
-// Wn[k * mA + i], Hn[k * nA + j] (what get_factor_kernel reads) and nothing else of the context; neither relies on what
-// the images hold in rows k >= K or in columns beyond m / n: components k >= K are replaced by exact zeros in registers,
-// and pad rows / columns of a tile only reach results that are never stored.
+// and ranked on the device (nbmf_top_n: top_n_kernel at the end of this file; DESIGN.md 4.7); and THETA_TILE, the 16 x 64
+// strip of Theta that predict_rows_kernel here and score_rows_kernel (nbmf_score_kernels.inc; DESIGN.md 4.8) both open with.
+// Included by nbmf_hip.hip after the other kernel files, before nbmf_score_kernels.inc.  The kernels that form products
+// read the natural padded factor images Wn[k * mA + i], Hn[k * nA + j] (what get_factor_kernel reads) and nothing else of
+// the context; none relies on what the images hold in rows k >= K or in columns beyond m / n: components k >= K are
+// replaced by exact zeros in registers, and pad rows / columns of a tile only reach results that are never stored.
 
 constexpr int PR_WAVES = 4;          // waves per workgroup of predict_rows_kernel: 4 strips of 64 columns, one 16-row tile
 constexpr int PR_STRIP = 64;         // columns per wave: four 16-column MFMA tiles on four accumulators
@@ -12,44 +13,53 @@ constexpr int PT_TILE = 32;          // k_major_kernel: 32 x 32 transpose tiles
 constexpr int TN_THREADS = 256;      // top_n_kernel: one workgroup per panel row, 256 columns per ordered chunk
 constexpr int TN_MAX = 256;          // most slots per row (NBMF_TOP_N_MAX): what the LDS entry list holds
 
-// Rows [prow0, prow0 + pnrows) of Theta, all n columns, into a staging panel whose row 0 is row prow0 and whose leading
-// dimension ldd is a multiple of 4 (doubles for OUT_U8 == 0, bytes otherwise).
+// The 16 x 64 strip of Theta = W^T H that one wave of a product kernel owns: what predict_rows_kernel and score_rows_kernel
+// (nbmf_score_kernels.inc) have in common, written once, so that the Theta one of them scores is the Theta the other
+// stores by construction.  The strip is rows i0 .. i0+15 on the image's 16-grid (blockIdx.x counts 16-row tiles from the
+// one that holds prow0) and columns j0 .. j0+63 (blockIdx.y, wave).  A wave whose strip starts at or beyond column JEND
+// (<= nA) leaves the kernel at once -- a whole wave, and no product kernel has a barrier.  What follows the macro is the
+// kernel's epilogue, which finds lr = l >> 4, lc = l & 15, i0, j0, jc = j0 + 4 lc and the finished accumulators acc[4].
+// A statement macro (as STAGE_DMA and MASKS_REQUEST of the sweeps), not a function: the tile is then the same statements
+// in both kernels, and the compiler's output for them is instruction for instruction what it was when each kernel
+// spelled them out (a function filling or returning acc changed the register assignment, by reference the counts too).
 //
-// One wave owns a 16 x 64 strip: rows i0 .. i0+15 on the image's 16-grid, columns j0 .. j0+63.  Its four MFMA tiles are
-// INTERLEAVED over the strip -- column c of tile t is j0 + 4c + t -- so that
+// The four MFMA tiles of a strip are INTERLEAVED over it -- column c of tile t is j0 + 4c + t -- so that
 //   - the four B operands of a lane are 4 consecutive doubles of one row of Hn: one 32-byte load, 512 contiguous bytes
 //     per group of 16 lanes (A: Wn[(k0 + (l >> 4)) * mA + i0 + (l & 15)], 128 contiguous bytes per group);
-//   - result register r of a lane holds Theta[i0 + (l >> 4) + 4r, j0 + 4(l & 15) + t] for t = 0..3 (the f64 C/D map:
-//     row = (l >> 4) + 4r, column = l & 15): 4 consecutive entries of one output row, stored as one 32-byte (doubles) or
-//     one 4-byte (bytes) access -- a store instruction writes 512 resp. 64 contiguous bytes per output row.
+//   - result register r of a lane holds Theta[i0 + (l >> 4) + 4r, jc + t] for t = 0..3 (the f64 C/D map: row =
+//     (l >> 4) + 4r, column = l & 15): 4 consecutive entries of one row, which an epilogue stores, or reads data for, as
+//     one 32-byte (doubles) or one 4-byte (bytes) access -- 512 resp. 64 contiguous bytes per row and instruction.
 // The k blocks are added in ascending order, one chain per tile: an entry's value depends on its row, its column and the
-// factors only, not on the panel or the request it was computed in.  Lanes whose k is >= K supply 0.0 to both operands
-// (the loop stops at the first multiple of 4 >= K, which is <= KP: no row of the images beyond KP is read).
+// factors only, not on the kernel, the panel or the request it was computed in.  Lanes whose k is >= K supply 0.0 to both
+// operands (the loop stops at the first multiple of 4 >= K, which is <= KP: no row of the images beyond KP is read).
+#define THETA_TILE(Wn, Hn, K, mA, nA, prow0, JEND)                                                                    \
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;                                                         \
+  const int lr = lane >> 4, lc = lane & 15;                                                                           \
+  const long long i0 = ((prow0) / 16 + blockIdx.x) * 16; /* < mA: the host sizes the grid */                          \
+  const long long j0 = ((long long)blockIdx.y * PR_WAVES + wave) * PR_STRIP;                                          \
+  if (j0 >= (JEND)) return;                                                                                           \
+  const long long jc = j0 + 4 * lc; /* this lane's four columns: jc .. jc+3 (< nA, a multiple of 128) */              \
+  d4 acc[4];                                                                                                          \
+  _Pragma("unroll") for (int t = 0; t < 4; ++t) acc[t] = d4{0.0, 0.0, 0.0, 0.0};                                      \
+  for (int k0 = 0; k0 < (K); k0 += 4) {                                                                               \
+    const int k = k0 + lr;                                                                                            \
+    double a = 0.0;                                                                                                   \
+    d4 b = d4{0.0, 0.0, 0.0, 0.0};                                                                                    \
+    if (k < (K)) {                                                                                                    \
+      a = (Wn)[(size_t)k * (mA) + i0 + lc];                                                                           \
+      b = *(const d4*)((Hn) + (size_t)k * (nA) + jc);                                                                 \
+    }                                                                                                                 \
+    _Pragma("unroll") for (int t = 0; t < 4; ++t) acc[t] = NBMF_MFMA(a, b[t], acc[t], 0, 0, 0);                       \
+  }
+
+// Rows [prow0, prow0 + pnrows) of Theta, all n columns, into a staging panel whose row 0 is row prow0 and whose leading
+// dimension ldd is a multiple of 4 (doubles for OUT_U8 == 0, bytes otherwise): the tile, then a lane's 4 x 4 entries
+// clipped, compared where bytes are asked for, and stored where their row is inside the panel.
 template <int OUT_U8>
 __global__ __launch_bounds__(PR_WAVES * 64) void predict_rows_kernel(
     const double* __restrict__ Wn, const double* __restrict__ Hn, int K, long long mA, long long nA, long long prow0,
     long long pnrows, long long ldd, int clip, double threshold, void* __restrict__ out) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lr = lane >> 4, lc = lane & 15;
-  const long long i0 = (prow0 / 16 + blockIdx.x) * 16;                                  // < mA: the host sizes the grid
-  const long long j0 = ((long long)blockIdx.y * PR_WAVES + wave) * PR_STRIP;
-  if (j0 >= nA) return;   // (no barrier below)
-  const long long jc = j0 + 4 * lc;   // this lane's four columns: jc .. jc+3 (< nA, a multiple of 128)
-
-  d4 acc[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = d4{0.0, 0.0, 0.0, 0.0};
-  for (int k0 = 0; k0 < K; k0 += 4) {
-    const int k = k0 + lr;
-    double a = 0.0;
-    d4 b = d4{0.0, 0.0, 0.0, 0.0};
-    if (k < K) {
-      a = Wn[(size_t)k * mA + i0 + lc];
-      b = *(const d4*)(Hn + (size_t)k * nA + jc);
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = NBMF_MFMA(a, b[t], acc[t], 0, 0, 0);
-  }
+  THETA_TILE(Wn, Hn, K, mA, nA, prow0, nA)
 
   if (jc >= ldd) return;   // ldd is a multiple of 4: jc .. jc+3 are inside the panel's row or all outside
 #pragma unroll

@@ -1,8 +1,8 @@
 // nbmf_score_kernels.inc -- the Bernoulli log-likelihood of Theta = W^T H against data, per row and per column
-// (nbmf_score_rows; DESIGN.md 4.8).  Included by nbmf_hip.hip after nbmf_predict_kernels.inc, whose tiling, operand loads
-// and constants (PR_WAVES, PR_STRIP) score_rows_kernel shares: the Theta it scores is bit for bit the entry
-// predict_rows_kernel<0> stores, but no Theta panel is ever written -- what leaves the kernel is one partial sum and one
-// count per (row, 64-column strip) and per (16-row block, column).  No floating-point atomics, no LDS, no barrier.
+// (nbmf_score_rows; DESIGN.md 4.8).  Included by nbmf_hip.hip after nbmf_predict_kernels.inc: score_rows_kernel opens with
+// that file's THETA_TILE, the very statements predict_rows_kernel opens with, so the Theta it scores is bit for bit the
+// entry predict_rows_kernel<0> stores -- but no Theta panel is ever written: what leaves the kernel is one partial sum and
+// one count per (row, 64-column strip) and per (16-row block, column).  No floating-point atomics, no LDS, no barrier.
 
 // The term of one observed entry, its logarithm's argument formed in exactly the order the header gives (additions only
 // around it: nothing to contract), with the device library's log (<= 1 ulp), not the sweeps' table logarithm.
@@ -24,8 +24,8 @@ __device__ __forceinline__ double score_term_f64(double th, double x, double eps
 // (bytes, leading dimension ldp, nonzero = observed; null: every entry is).  What the panels hold in columns n .. ldp-1 is
 // read and never used.
 //
-// Tiling and k loop are predict_rows_kernel's: after the loop, register r of a lane holds Theta[i0 + (l >> 4) + 4r,
-// jc + t], t = 0..3, jc = j0 + 4 (l & 15) -- 4 rows x 4 consecutive columns, whose data are one 4-byte word (one 32-byte
+// After THETA_TILE (nbmf_predict_kernels.inc) register r of a lane's acc[t] holds Theta[i0 + (l >> 4) + 4r, jc + t],
+// t = 0..3, jc = j0 + 4 (l & 15) -- 4 rows x 4 consecutive columns, whose data are one 4-byte word (one 32-byte
 // access for doubles) per row, and the mask likewise.  term[r][t] is the entry's term, or nothing (+0.0, count 0) where
 // the entry is unobserved, its column is >= n or its row is outside the panel.
 //   rows:    ((term[r][0] + term[r][1]) + term[r][2]) + term[r][3], then the xor butterfly 1, 2, 4, 8 over the 16 lanes
@@ -44,27 +44,7 @@ __global__ __launch_bounds__(PR_WAVES * 64) void score_rows_kernel(
     long long prow0, long long pnrows, long long ldp, int clip, double eps, const void* __restrict__ xd,
     const unsigned char* __restrict__ md, double* __restrict__ row_part, int* __restrict__ row_cnt,
     double* __restrict__ col_part, int* __restrict__ col_cnt) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lr = lane >> 4, lc = lane & 15;
-  const long long i0 = (prow0 / 16 + blockIdx.x) * 16;                                  // < mA: the host sizes the grid
-  const long long j0 = ((long long)blockIdx.y * PR_WAVES + wave) * PR_STRIP;
-  if (j0 >= ldp) return;              // (ldp <= nA)
-  const long long jc = j0 + 4 * lc;   // this lane's four columns: jc .. jc+3 (< nA, a multiple of 128)
-
-  d4 acc[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = d4{0.0, 0.0, 0.0, 0.0};
-  for (int k0 = 0; k0 < K; k0 += 4) {
-    const int k = k0 + lr;
-    double a = 0.0;
-    d4 b = d4{0.0, 0.0, 0.0, 0.0};
-    if (k < K) {
-      a = Wn[(size_t)k * mA + i0 + lc];
-      b = *(const d4*)(Hn + (size_t)k * nA + jc);
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = NBMF_MFMA(a, b[t], acc[t], 0, 0, 0);
-  }
+  THETA_TILE(Wn, Hn, K, mA, nA, prow0, ldp)   // (ldp <= nA)
 
   const bool in_panel = jc < ldp;   // ldp is a multiple of 4: jc .. jc+3 are inside the panel's row or all outside
   double term[4][4];

@@ -219,38 +219,69 @@ def test_context_refuses_a_bad_eps_and_an_empty_request(bare_context):
         ctx.score_rows(x, rows=False, cols=False)
 
 
-def test_score_panel_passes_a_wider_array_through():
+def test_row_array_passes_a_wider_array_through():
     from nbmf_mm_amd import _hip
+    score_panel = lambda a, nrows, n: _hip.row_array(a, nrows, n, "x", _hip.ANY_KINDS)   # noqa: E731
     wide = np.zeros((12, 20), dtype=bool)
-    view, kind, ld = _hip.score_panel(wide[:, 3:12], 12, 9)
+    view, kind, ld = score_panel(wide[:, 3:12], 12, 9)
     assert (kind, ld) == (_hip.DATA_U8, 20) and view.dtype == np.uint8 and np.shares_memory(view, wide)
     widef = np.zeros((12, 20))
-    view, kind, ld = _hip.score_panel(widef[:, 3:12], 12, 9)
+    view, kind, ld = score_panel(widef[:, 3:12], 12, 9)
     assert (kind, ld) == (_hip.DATA_F64, 20) and np.shares_memory(view, widef)
-    assert _hip.score_panel(np.ones((12, 9), dtype=np.uint8), 12, 9)[1:] == (_hip.DATA_U8, 9)
-    assert _hip.score_panel(widef[4:5, :9], 1, 9)[2] == 9                    # one row: its stride does not matter
-    assert _hip.score_panel(np.zeros((0, 9)), 0, 9)[2] == 9
+    assert score_panel(np.ones((12, 9), dtype=np.uint8), 12, 9)[1:] == (_hip.DATA_U8, 9)
+    assert score_panel(widef[4:5, :9], 1, 9)[2] == 9                         # one row: its stride does not matter
+    assert score_panel(np.zeros((0, 9)), 0, 9)[2] == 9
+
+
+def test_row_array_checks_the_out_of_predict_rows(bare_context):
+    """The float64 ``out`` of ``predict_rows`` goes through the same rule: a 12 x 9 slice of a 12 x 16 array, one row and
+    zero rows are passed through with the right leading dimension, nothing copied; a column-major array is refused."""
+    from nbmf_mm_amd import _hip
+    out_array = lambda a, nrows: _hip.row_array(a, nrows, 9, "out", (np.float64,))   # noqa: E731
+    wide = np.zeros((12, 16))
+    view, kind, ld = out_array(wide[:, :9], 12)
+    assert (kind, ld) == (_hip.DATA_F64, 16) and view.dtype == np.float64 and np.shares_memory(view, wide)
+    view, kind, ld = out_array(wide[4:5, :9], 1)                             # one row: its stride does not matter
+    assert (kind, ld) == (_hip.DATA_F64, 9) and np.shares_memory(view, wide)
+    assert out_array(wide[3:3, :9], 0)[1:] == (_hip.DATA_F64, 9)
+    with pytest.raises(ValueError, match="out must have unit stride"):
+        out_array(np.asfortranarray(np.zeros((12, 9))), 12)
+    with pytest.raises(ValueError, match="out must be a float64 array"):
+        out_array(np.zeros((12, 9), dtype=np.uint8), 12)
+    with pytest.raises(ValueError, match="out must have shape"):
+        out_array(wide[:, :8], 12)
+    # ... and predict_rows refuses before it touches the device: a malformed out, a list (it could not be written in
+    # place), rows outside the matrix (the text the library itself gives)
+    ctx = bare_context
+    with pytest.raises(ValueError, match="stride"):
+        ctx.predict_rows(out=np.asfortranarray(np.zeros((12, 9))))
+    with pytest.raises(ValueError, match="out must be a bool or uint8 array"):
+        ctx.predict_rows(threshold=0.5, out=np.zeros((12, 9)))
+    with pytest.raises(ValueError, match="out must be a NumPy array"):
+        ctx.predict_rows(out=[[0.0] * 9] * 12)
+    with pytest.raises(ValueError, match=r"rows \[11, 11 \+ 2\) are not inside \[0, 12\)"):
+        ctx.predict_rows(11, 2)
 
 
 # ---- _solver: how a row block reaches the device ----------------------------------------------------------------------------
-def test_score_block_picks_the_narrowest_exact_form():
+def test_row_block_picks_the_narrowest_exact_form():
     import scipy.sparse as sp
     from nbmf_mm_amd import _solver
     r = np.random.default_rng(3)
     xb = (r.random((40, 7)) < 0.4).astype(np.float64)
-    got = _solver._score_block(xb, 16, 16, False)
+    got = _solver._row_block(xb, 16, 16, False)
     assert got.dtype == np.uint8 and np.array_equal(got, xb[16:32])
     xr = xb.copy()
     xr[20, 3] = 0.5
-    assert _solver._score_block(xr, 16, 16, False).dtype == np.float64 and _solver._score_block(xr, 0, 16, False).dtype == np.uint8
+    assert _solver._row_block(xr, 16, 16, False).dtype == np.float64 and _solver._row_block(xr, 0, 16, False).dtype == np.uint8
     u8 = xb.astype(np.uint8)
-    assert np.shares_memory(_solver._score_block(u8, 16, 16, False), u8)                    # bytes: passed as they are
-    got = _solver._score_block(sp.csr_matrix(xr), 16, 24, False)
+    assert np.shares_memory(_solver._row_block(u8, 16, 16, False), u8)                      # bytes: passed as they are
+    got = _solver._row_block(sp.csr_matrix(xr), 16, 24, False)
     assert got.dtype == np.float64 and np.array_equal(got, xr[16:40])
-    mk = _solver._score_block(sp.csr_matrix(3.0 * xb), 32, 8, True)
+    mk = _solver._row_block(sp.csr_matrix(3.0 * xb), 32, 8, True)
     assert mk.dtype == np.bool_ and np.array_equal(mk, xb[32:40] != 0)
-    assert np.array_equal(_solver._score_block(2.5 * xb, 0, 40, True), xb != 0)             # any numeric mask: nonzero = observed
-    t = _solver._score_block(np.asfortranarray(u8), 0, 40, False)
+    assert np.array_equal(_solver._row_block(2.5 * xb, 0, 40, True), xb != 0)               # any numeric mask: nonzero = observed
+    t = _solver._row_block(np.asfortranarray(u8), 0, 40, False)
     assert t.flags.c_contiguous and np.array_equal(t, u8)
 
 

@@ -165,16 +165,17 @@ def test_context_refuses_a_bad_exclude(bare_context):
         ctx.top_n(3, exclude=np.broadcast_to(np.zeros(9, dtype=bool), (12, 9)))
 
 
-def test_exclude_bytes_passes_a_wider_array_through():
+def test_row_array_passes_a_wider_exclude_through():
     from nbmf_mm_amd import _hip
+    exclude_bytes = lambda a, nrows, n: _hip.row_array(a, nrows, n, "exclude", _hip.BYTE_KINDS)[::2]   # noqa: E731
     wide = np.zeros((12, 20), dtype=bool)
-    view, ldx = _hip.exclude_bytes(wide[:, 3:12], 12, 9)
+    view, ldx = exclude_bytes(wide[:, 3:12], 12, 9)
     assert ldx == 20 and view.dtype == np.uint8 and np.shares_memory(view, wide)
-    view, ldx = _hip.exclude_bytes(np.ones((12, 9), dtype=np.uint8), 12, 9)
+    view, ldx = exclude_bytes(np.ones((12, 9), dtype=np.uint8), 12, 9)
     assert ldx == 9
-    view, ldx = _hip.exclude_bytes(wide[4:5, :9], 1, 9)                    # one row: its stride does not matter
+    view, ldx = exclude_bytes(wide[4:5, :9], 1, 9)                         # one row: its stride does not matter
     assert ldx == 9
-    view, ldx = _hip.exclude_bytes([[True, False]], 1, 2)
+    view, ldx = exclude_bytes([[True, False]], 1, 2)
     assert view.tolist() == [[1, 0]]
 
 
