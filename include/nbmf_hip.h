@@ -274,6 +274,27 @@ int nbmf_score_rows(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int clip_theta, 
                     double* row_ll, int64_t* row_obs,   /* nrows each, either may be NULL */
                     double* col_ll, int64_t* col_obs);  /* n each, either may be NULL */
 
+/* The observed zeros and the observed ones of the rows [row0, row0 + nrows) of the data, counted by the Theta they got: the
+ * two integer histograms that ROC AUC and a calibration curve are functions of.  theta[i, j] is bit for bit the entry
+ * nbmf_predict_rows(..., clip_theta = 1, NBMF_PREDICT_F64, ...) returns: the clip to [0, 1] is always on.  An entry is
+ * OBSERVED if mask is NULL or mask[(i - row0) * ldmask + j] != 0; its class is c = (x[(i - row0) * ldx + j] != 0), and with
+ *   p = theta * bins   (one rounded double multiplication),   b = (long long)p,   b = bins - 1 where b >= bins
+ * it adds 1 to hist[c * bins + b]: bin b holds the thetas in [b / bins, (b + 1) / bins) -- a theta exactly on an edge
+ * belongs to the upper bin -- and the last bin holds theta = 1 as well.  A NaN theta is in neither histogram: it adds 1 to
+ * nan_count[c] (nan_count may be NULL).  Unobserved entries count nowhere, so hist sums to the observed entries less the NaN
+ * ones.  x and mask are nrows x n bytes, row-major with leading dimensions ldx and ldmask, both >= n; nothing beyond column
+ * n - 1 is read.  The counts are exact integers: they do not depend on row0's alignment, on the panels (NBMF_PREDICT_PANEL_ROWS,
+ * as nbmf_predict_rows) or on the order the device adds them in, and the same call twice gives the same arrays (integer
+ * adds only, no floating-point atomics); the counts of two disjoint row ranges add up to those of their union.
+ * NBMF_ERR_ARG for rows outside [0, m), bins outside [1, NBMF_HIST_MAX_BINS], ldx < n, ldmask < n with a mask, a NULL hist,
+ * or a NULL x with nrows > 0 -- no output is touched then; nrows == 0 reads nothing and zero-fills the outputs.  Same state
+ * rules and synchronisation as nbmf_predict_rows. */
+#define NBMF_HIST_MAX_BINS 1024
+int nbmf_theta_hist(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int bins,
+                    const uint8_t* x, int64_t ldx,
+                    const uint8_t* mask /* NULL: all observed; nonzero = observed */, int64_t ldmask,
+                    int64_t* hist /* [2][bins]: class 0 first */, int64_t* nan_count /* [2], may be NULL */);
+
 /* Multi-GPU, one process (and one context) per GPU.  The internal matrix Y is split over the ranks along
  *   shard_axis 0: its ROWS    -> W[:, rows] is local, H is replicated; each iteration all-reduces the k x n
  *                 H-step products [P1 | P2 | loglik] (2*K*N+1 doubles) before the H-update;

@@ -8,9 +8,9 @@ import numpy as np
 from sklearn.base import BaseEstimator, TransformerMixin
 from sklearn.utils import check_array
 
-from . import _hip
-from ._solver import (device_predict, device_score, device_score_samples, device_top_n, nbmf_mm_restarts, nbmf_mm_solver,
-                      w_only_transform)
+from . import _hip, _metrics
+from ._solver import (device_predict, device_score, device_score_samples, device_theta_hist, device_top_n, nbmf_mm_restarts,
+                      nbmf_mm_solver, w_only_transform)
 from ._utils import check_is_fitted
 
 # Accepted spellings of the two orientations: the exact strings of src/nbmf_mm/_base.py:127-137
@@ -285,6 +285,32 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         """exp(-score) (_base.py:249-265)."""
         return np.exp(-self.score(X, mask))
 
+    def _scored_inputs(self, X, mask, W, H, exact=False):
+        """``(X, mask)`` of a request that sets Theta = ``predict_proba(W)`` against data (:meth:`score_samples`, the
+        histogram methods), validated without a device: X through fit's checks with their errors in fit's order -- shape,
+        then sklearn's own NaN / inf error, then "X must be binary" for anything outside [0, 1], with ``exact`` for
+        anything but 0 and 1 -- and the mask's dtype and shape."""
+        X = self._validated(X, keep_sparse=True)
+        want = (W.shape[0], H.shape[1])
+        if tuple(X.shape) != want:
+            raise ValueError(f"X has shape {tuple(X.shape)}, the request describes {want}")
+        inside = (lambda v: (v == 0) | (v == 1)) if exact else (lambda v: (v >= 0) & (v <= 1))
+        if hasattr(X, "toarray"):
+            if X.nnz and not np.all(inside(X.data)):
+                raise ValueError("X must be binary")                  # fit's check of the stored values
+        elif X.dtype != np.bool_ and not np.all(inside(X)):
+            if X.dtype != np.uint8:
+                check_array(X, dtype=None)                            # NaN / inf: sklearn's own error first, as in fit
+            raise ValueError("X must be binary")
+        if mask is not None:
+            if not hasattr(mask, "toarray"):
+                mask = np.asarray(mask)
+            if mask.dtype != np.bool_ and not np.issubdtype(mask.dtype, np.number):
+                raise ValueError(f"mask must be a bool or numeric matrix (got dtype {mask.dtype})")
+            if mask.ndim != 2 or tuple(mask.shape) != want:
+                raise ValueError(f"mask has shape {tuple(mask.shape)}, the request describes {want}")
+        return X, mask
+
     def score_samples(self, X, mask=None, W=None, axis=0, return_counts=False):
         """Mean log-likelihood per observed entry of every row of ``X`` (``axis=0``) or of every feature (``axis=1``) under
         ``predict_proba(W)``, summed on the GPU: a float64 1-D array, NaN where nothing is observed; with
@@ -301,28 +327,61 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         W, H = self._prediction_factors(W)
         if axis not in (0, 1) or isinstance(axis, (bool, np.bool_)):
             raise ValueError(f"axis must be 0 (rows) or 1 (features) (got {axis!r})")
-        X = self._validated(X, keep_sparse=True)
-        want = (W.shape[0], H.shape[1])
-        if tuple(X.shape) != want:
-            raise ValueError(f"X has shape {tuple(X.shape)}, the request describes {want}")
-        if hasattr(X, "toarray"):
-            if X.nnz and not (X.data.min() >= 0 and X.data.max() <= 1):
-                raise ValueError("X must be binary")                  # fit's check of the stored values
-        elif X.dtype != np.bool_ and not np.all((X >= 0) & (X <= 1)):
-            if X.dtype != np.uint8:
-                check_array(X, dtype=None)                            # NaN / inf: sklearn's own error first, as in fit
-            raise ValueError("X must be binary")
-        if mask is not None:
-            if not hasattr(mask, "toarray"):
-                mask = np.asarray(mask)
-            if mask.dtype != np.bool_ and not np.issubdtype(mask.dtype, np.number):
-                raise ValueError(f"mask must be a bool or numeric matrix (got dtype {mask.dtype})")
-            if mask.ndim != 2 or tuple(mask.shape) != want:
-                raise ValueError(f"mask has shape {tuple(mask.shape)}, the request describes {want}")
+        X, mask = self._scored_inputs(X, mask, W, H)
         sums, counts = device_score_samples(W, H, X, mask=mask, axis=int(axis), device=self.device)
         with np.errstate(invalid="ignore", divide="ignore"):
             scores = np.where(counts > 0, sums / np.maximum(counts, 1), np.nan)
         return (scores, counts) if return_counts else scores
+
+    # -- how good the predictions are: class histograms of Theta on the device -----------------------------
+    def _theta_hist(self, X, mask, W, bins):
+        W, H = self._prediction_factors(W)
+        X, mask = self._scored_inputs(X, mask, W, H, exact=True)
+        hist, nan_count = device_theta_hist(W, H, X, mask=mask, bins=bins, device=self.device)
+        if nan_count.any():
+            raise ValueError(f"Theta has NaN entries ({int(nan_count.sum())} of the observed ones): the factors are not finite")
+        return hist
+
+    def theta_histogram(self, X, mask=None, W=None, bins=256):
+        """The observed entries of the binary ``X``, counted on the GPU by class and by ``predict_proba(W)``:
+        ``(hist, edges)``, ``hist`` int64 of shape ``(2, bins)`` -- ``hist[0]`` the observed zeros, ``hist[1]`` the observed
+        ones -- and ``edges = np.arange(bins + 1) / bins``.  Bin b holds the Thetas with ``min(int(Theta * bins), bins - 1)
+        == b``, that is ``[edges[b], edges[b + 1])``, the last one closed at 1.  ``bins`` is at most 1024.  ``W`` defaults
+        to ``W_``; ``X`` and ``mask`` as in :meth:`score_samples` (``mask`` nonzero = counted), except that ``X`` must be
+        exactly 0 / 1.  HELD-OUT USE: ``fit(X, mask=train)``, then ``theta_histogram(X, mask=held_out)`` with ``held_out``
+        the complement of ``train`` -- the two histograms of the entries the fit never saw, of which :meth:`roc_auc` and
+        :meth:`calibration_curve` are functions.  The counts are exact integers: they do not depend on how the input is
+        streamed (sparse and float input goes up in row blocks and gives exactly the arrays of dense bool input) or on the
+        order the device adds them in.  Raises ``ValueError("Theta has NaN entries ...")`` if any observed Theta is NaN.
+        Only ``2 * bins + 2`` integers leave the device, and X goes up at one byte per entry."""
+        bins = _hip.hist_bins(bins)
+        return self._theta_hist(X, mask, W, bins), np.arange(bins + 1) / bins
+
+    def roc_auc(self, X, mask=None, W=None, bins=1024, return_slack=False):
+        """The ROC AUC of ``predict_proba(W)`` as a ranking of the observed ones of ``X`` above its observed zeros, from
+        the ``bins``-bin :meth:`theta_histogram`: the AUC of the binned Thetas, ties counted one half
+        (``_metrics.auc_from_hist``).  With ``return_slack`` the pair ``(auc, slack)``: the exact AUC of the unbinned
+        Thetas lies within ``slack`` of ``auc`` (half the share of (zero, one) pairs that fall into one bin).  NaN where
+        a class has no observed entry.  HELD-OUT USE: ``fit(X, mask=train)``, then ``roc_auc(X, mask=held_out)``.  No
+        score leaves the device and nothing is sorted: the cost is :meth:`theta_histogram`'s."""
+        bins = _hip.hist_bins(bins)
+        auc, slack = _metrics.auc_from_hist(self._theta_hist(X, mask, W, bins))
+        return (auc, slack) if return_slack else auc
+
+    def calibration_curve(self, X, mask=None, W=None, n_bins=10, resolution=100):
+        """``(prob_true, prob_pred, counts)`` over ``n_bins`` equal-width bins of [0, 1]: the share of ones among the
+        observed entries whose ``predict_proba(W)`` lies in the bin, their mean predicted probability, and how many they
+        are (int64) -- is a predicted 0.3 a one 30 % of the time?  From a :meth:`theta_histogram` of ``n_bins *
+        resolution`` fine bins (at most 1024: ``ValueError`` beyond), ``resolution`` fine bins per coarse one
+        (``_metrics.calibration_from_hist``): ``counts`` and ``prob_true`` are exact, ``prob_pred`` is within
+        ``1 / (2 n_bins resolution)`` of the bin's true mean.  Bin q is ``[q / n_bins, (q + 1) / n_bins)``, the last one
+        closed at 1; NaN where a bin is empty.  HELD-OUT USE: ``fit(X, mask=train)``, then
+        ``calibration_curve(X, mask=held_out)``."""
+        n_bins = _hip.hist_bins(n_bins, name="n_bins")
+        resolution = _hip.hist_bins(resolution, name="resolution")
+        if n_bins * resolution > _hip.HIST_MAX_BINS:
+            raise ValueError(f"n_bins * resolution must be at most {_hip.HIST_MAX_BINS} (got {n_bins} * {resolution})")
+        return _metrics.calibration_from_hist(self._theta_hist(X, mask, W, n_bins * resolution), n_bins)
 
 
 # alias kept for backwards compatibility (_base.py:269)

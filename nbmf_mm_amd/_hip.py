@@ -37,11 +37,12 @@ SYMBOLS = [
     "nbmf_set_progress", "nbmf_device_synchronize", "nbmf_small_stats", "nbmf_generate_slice", "nbmf_set_storage",
     "nbmf_set_exchange_panels", "nbmf_set_peer_timeout_ms", "nbmf_run_batch", "nbmf_batch_stats", "nbmf_sweep_info",
     "nbmf_upload_v", "nbmf_selftest_mfma_peak", "nbmf_engine_stats", "nbmf_source_hash", "nbmf_comm_info", "nbmf_cancel", "nbmf_variant_stats", "nbmf_device_bus_id",
-    "nbmf_predict_at", "nbmf_predict_rows", "nbmf_top_n", "nbmf_score_rows",
+    "nbmf_predict_at", "nbmf_predict_rows", "nbmf_top_n", "nbmf_score_rows", "nbmf_theta_hist",
 ]
 DATA_F64, DATA_U8, DATA_F32 = 0, 1, 2
 PREDICT_F64, PREDICT_U8 = 0, 1
 TOP_N_MAX = 256
+HIST_MAX_BINS = 1024
 
 
 #: int fn(void* user, double* buf, int64 count) -- in-place sum over ranks on a host buffer
@@ -178,6 +179,7 @@ def load():
     lib.nbmf_top_n.argtypes = [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64]
     lib.nbmf_score_rows.argtypes = [c_void_p, c_int64, c_int64, c_int, c_double, c_void_p, c_int, c_int64, c_void_p, c_int64,
                                     c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.nbmf_theta_hist.argtypes = [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]
     for name in SYMBOLS:
         if name not in ("nbmf_last_error", "nbmf_source_hash"):
             getattr(lib, name).restype = c_int
@@ -262,6 +264,16 @@ def top_n_count(top, name="top"):
     return int(top)
 
 
+def hist_bins(bins, name="bins"):
+    """``bins`` of ``theta_hist`` as an int, after the checks that need no device: an integer (not a bool) in
+    ``[1, HIST_MAX_BINS]``.  Raises ``ValueError`` otherwise."""
+    if isinstance(bins, (bool, np.bool_)) or not isinstance(bins, (int, np.integer)):
+        raise ValueError(f"{name} must be an integer (got {bins!r})")
+    if not 1 <= int(bins) <= HIST_MAX_BINS:
+        raise ValueError(f"{name} must be in [1, {HIST_MAX_BINS}] (got {int(bins)})")
+    return int(bins)
+
+
 #: the dtypes a row array may have: one byte per entry (passed to the library as uint8), or float64
 BYTE_KINDS = (np.bool_, np.uint8)
 ANY_KINDS = BYTE_KINDS + (np.float64,)
@@ -269,8 +281,8 @@ ANY_KINDS = BYTE_KINDS + (np.float64,)
 
 def row_array(a, nrows, n, name, kinds):
     """A caller's ``(nrows, n)`` array as the row-slab calls of the library take it -- the ``out`` of ``predict_rows``,
-    the ``exclude`` of ``top_n``, the data and the mask of ``score_rows``: ``(array, kind, ld)``, ``kind`` DATA_U8 (a bool
-    or uint8 array, returned as its uint8 view) or DATA_F64, ``ld`` the leading dimension in elements.  The dtype must be
+    the ``exclude`` of ``top_n``, the data and the mask of ``score_rows`` and of ``theta_hist``: ``(array, kind, ld)``,
+    ``kind`` DATA_U8 (a bool or uint8 array, returned as its uint8 view) or DATA_F64, ``ld`` the leading dimension in elements.  The dtype must be
     one of ``kinds`` (BYTE_KINDS, ANY_KINDS or ``(np.float64,)``), the shape ``(nrows, n)``, the stride along a row one
     element, the row stride at least n elements and whole elements -- a slice of a wider array is passed through as it is,
     nothing is copied.  The row stride of a single row or of an empty array is ignored: ``ld = n``.  Raises ``ValueError``
@@ -546,6 +558,29 @@ class Context:
         _check(self._lib.nbmf_score_rows(self._h, row0, nrows, int(bool(clip_theta)), eps, ptr(x), x_kind, ldx, mptr, ldm,
                                          ptr(row_ll), ptr(row_obs), ptr(col_ll), ptr(col_obs)))
         return row_ll, row_obs, col_ll, col_obs
+
+    def theta_hist(self, x, mask=None, row0=0, nrows=None, bins=256):
+        """The observed entries of the rows ``[row0, row0 + nrows)`` of the binary data ``x``, counted on the device by
+        class and by the Theta they got (``nbmf_theta_hist``): ``(hist, nan_count)``, int64 of shape ``(2, bins)`` and
+        ``(2,)``.  ``hist[c, b]`` counts the observed entries of class ``c = (x != 0)`` whose Theta, clipped to [0, 1], has
+        ``min(int(theta * bins), bins - 1) == b``: bin b is ``[b / bins, (b + 1) / bins)``, the last one holds 1 as well.
+        A NaN Theta is counted in ``nan_count[c]`` instead.  ``x``: bool / uint8 of shape ``(nrows, n)``; ``mask``: the
+        same, nonzero = observed, None: every entry.  Both may be slices of wider arrays (unit stride along a row); nothing
+        is copied on the host.  Theta is bit for bit what :meth:`predict_rows` returns.  The counts are exact: the same
+        whatever the panels and the order of the device's additions, and those of disjoint row ranges add up.  Only
+        ``2 * bins + 2`` integers come back from the device."""
+        row0, nrows = self._rows(row0, nrows)
+        bins = hist_bins(bins)
+        x, _, ldx = row_array(x, nrows, self.n, "x", BYTE_KINDS)
+        mptr, ldm = None, 0
+        if mask is not None:
+            mask, _, ldm = row_array(mask, nrows, self.n, "mask", BYTE_KINDS)
+            mptr = mask.ctypes.data_as(c_void_p)
+        hist = np.empty((2, bins), dtype=np.int64)
+        nan_count = np.empty(2, dtype=np.int64)
+        _check(self._lib.nbmf_theta_hist(self._h, row0, nrows, bins, x.ctypes.data_as(c_void_p), ldx, mptr, ldm,
+                                         hist.ctypes.data_as(c_void_p), nan_count.ctypes.data_as(c_void_p)))
+        return hist, nan_count
 
     def comm_init(self, uid: bytes, nranks: int, rank: int, shard_axis: int = 0):
         """Attach an RCCL communicator; shard_axis 0 = rows of the internal Y are split, 1 = columns."""

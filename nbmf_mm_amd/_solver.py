@@ -328,6 +328,20 @@ def _row_block(A, r0, nr, is_mask):
     return a
 
 
+def _sliceable(X, mask):
+    """``(X, mask, one_call)``: the data and the mask of :func:`device_score_samples` / :func:`device_theta_hist` in a form
+    whose row blocks ``_row_block`` can take (sparse as CSR, anything else an ndarray), and whether they can go to the
+    device in one call as they are: both dense bool / uint8 (or no mask)."""
+    byte = lambda a: a is None or (not hasattr(a, "toarray") and a.dtype in (np.bool_, np.uint8))   # noqa: E731
+    if hasattr(X, "toarray"):
+        X = X.tocsr()
+    elif not isinstance(X, np.ndarray):
+        X = np.asarray(X)
+    if mask is not None:
+        mask = mask.tocsr() if hasattr(mask, "toarray") else np.asarray(mask)
+    return X, mask, byte(X) and byte(mask)
+
+
 def device_score_samples(W, H, X, mask=None, axis=0, device=0):
     """The log-likelihood of Theta = clip(``W @ H``, 0, 1) against ``X`` (eps = 1e-8, as ``NBMFMM.score``), summed on the
     GPU (``Context.score_rows``) over the observed entries of every row (``axis=0``) or of every feature (``axis=1``):
@@ -338,15 +352,9 @@ def device_score_samples(W, H, X, mask=None, axis=0, device=0):
     data goes as uint8 where the block is exactly {0, 1} and as float64 otherwise.  A row's result does not depend on the
     blocks.  For ``axis=1`` the blocks' sums and counts are added on the host in ascending order: feature scores of
     block-streamed input equal the one-call result to rounding, not bit for bit."""
-    byte = lambda a: a is None or (not hasattr(a, "toarray") and a.dtype in (np.bool_, np.uint8))   # noqa: E731
-    if hasattr(X, "toarray"):
-        X = X.tocsr()
-    elif not isinstance(X, np.ndarray):
-        X = np.asarray(X)
-    if mask is not None:
-        mask = mask.tocsr() if hasattr(mask, "toarray") else np.asarray(mask)
+    X, mask, one_call = _sliceable(X, mask)
     with _factors_only(W, H, device) as (ctx, m, n):
-        block = m if byte(X) and byte(mask) else max(16, SCORE_SAMPLES_BLOCK_BYTES // (8 * max(n, 1)) // 16 * 16)
+        block = m if one_call else max(16, SCORE_SAMPLES_BLOCK_BYTES // (8 * max(n, 1)) // 16 * 16)
         sums = np.zeros(n if axis else m, dtype=np.float64)
         counts = np.zeros(n if axis else m, dtype=np.int64)
         for r0 in range(0, m, max(block, 1)):
@@ -360,3 +368,30 @@ def device_score_samples(W, H, X, mask=None, axis=0, device=0):
             else:
                 sums[r0:r0 + nr], counts[r0:r0 + nr] = rl, ro
     return sums, counts
+
+
+def device_theta_hist(W, H, X, mask=None, bins=256, device=0):
+    """The observed entries of the binary ``X``, counted on the GPU (``Context.theta_hist``) by class and by the bin of
+    Theta = clip(``W @ H``, 0, 1) they fall in: ``(hist int64 (2, bins), nan_count int64 (2,))``.  ``W``, ``H`` as in
+    :func:`device_predict`; ``X`` and ``mask`` (nonzero = observed) dense or scipy-sparse of shape ``(rows, features)``,
+    already validated.  Factors only: no context holds the data.  Dense bool / uint8 input with a bool / uint8 (or no)
+    mask goes to the device in one call as it is.  Anything else goes in row blocks of at most
+    ``SCORE_SAMPLES_BLOCK_BYTES``: sparse blocks are made dense, a block of another dtype goes as uint8 when it is exactly
+    {0, 1} and is otherwise not binary: ``ValueError("X must be binary")``.  The blocks' counts are added on the host as
+    int64 -- unlike the feature sums of :func:`device_score_samples`, integers: block-streamed input gives exactly the
+    arrays of the one-call form."""
+    X, mask, one_call = _sliceable(X, mask)
+    with _factors_only(W, H, device) as (ctx, m, n):
+        block = m if one_call else max(16, SCORE_SAMPLES_BLOCK_BYTES // (8 * max(n, 1)) // 16 * 16)
+        hist = np.zeros((2, bins), dtype=np.int64)
+        nan_count = np.zeros(2, dtype=np.int64)
+        for r0 in range(0, m, max(block, 1)):
+            nr = min(block, m - r0)
+            x = _row_block(X, r0, nr, False)
+            if x.dtype == np.float64:
+                raise ValueError("X must be binary")
+            mk = None if mask is None else _row_block(mask, r0, nr, True)
+            h, c = ctx.theta_hist(x, mk, r0, nr, bins=bins)
+            hist += h
+            nan_count += c
+    return hist, nan_count

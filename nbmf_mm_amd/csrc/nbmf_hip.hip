@@ -321,6 +321,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 #include "nbmf_small_kernel.inc"
 #include "nbmf_predict_kernels.inc"
 #include "nbmf_score_kernels.inc"
+#include "nbmf_hist_kernels.inc"
 
 }  // namespace
 
@@ -2477,7 +2478,8 @@ int one_shot(nbmf_ctx* c, bool with_prior, int strict, int clip, bool collect_ti
 // (also the single-launch engine's end-of-run guard: small_guard)
 int loss_by_launches(nbmf_ctx* c, double* loss) { return one_shot(c, /*with_prior=*/true, 0, 0, /*collect_timing=*/true, loss); }
 
-// ---- shared by the four entry points that read Theta back: nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows
+// ---- shared by the five entry points that read Theta back: nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows,
+// nbmf_theta_hist
 // (DESIGN.md 4.6).  Staging of one such call, from the pool: given back when the call returns, on every path, after the
 // stream has drained (a pooled block may be handed to the next caller at once).
 struct PredictStage {
@@ -2496,7 +2498,7 @@ struct PredictStage {
   }
 };
 
-// The checks all four share, in the order the header gives them: factors, not data (so not ready()).
+// The checks all five share, in the order the header gives them: factors, not data (so not ready()).
 int predict_ready(nbmf_ctx* c) {
   if (!c) return fail(NBMF_ERR_ARG, "null context");
   if (!c->have_factors) return fail(NBMF_ERR_STATE, "no factors on the device");
@@ -2504,7 +2506,7 @@ int predict_ready(nbmf_ctx* c) {
   return NBMF_OK;
 }
 
-int check_rows(nbmf_ctx* c, int64_t row0, int64_t nrows) {   // the three row-slab entry points: all but nbmf_predict_at
+int check_rows(nbmf_ctx* c, int64_t row0, int64_t nrows) {   // the four row-slab entry points: all but nbmf_predict_at
   if (nrows < 0 || row0 < 0 || row0 > c->m || nrows > c->m - row0)
     return fail(NBMF_ERR_ARG, "rows [%lld, %lld + %lld) are not inside [0, %lld)", (long long)row0, (long long)row0, (long long)nrows,
                 (long long)c->m);
@@ -2565,6 +2567,16 @@ hipError_t launch_score_panel(nbmf_ctx* c, const RowPanels& pl, long long p0, lo
   return hipGetLastError();
 }
 
+// The same rows of Theta, clipped, counted by class and bin against the staged data and mask panels (nbmf_theta_hist).
+hipError_t launch_hist_panel(nbmf_ctx* c, const RowPanels& pl, long long p0, long long pn, int bins, const unsigned char* x_d,
+                             const unsigned char* m_d, int copies, unsigned long long* total_d) {
+  const size_t lds = sizeof(unsigned int) * PR_WAVES * (2 * (size_t)bins + 2);   // a histogram per wave: <= 32 KiB + 32 bytes
+  hipLaunchKernelGGL(theta_hist_kernel, pl.grid(p0, pn), dim3(PR_WAVES * 64), lds, c->stream, (const double*)c->Wn,
+                     (const double*)c->Hn, c->k, (long long)c->mA, (long long)c->nA, (long long)c->n, p0, pn, pl.ldp, bins, x_d, m_d,
+                     copies, total_d);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -2572,7 +2584,7 @@ hipError_t launch_score_panel(nbmf_ctx* c, const RowPanels& pl, long long p0, lo
 // ------------------------------------------------------------------------------------------
 extern "C" {
 
-int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows: compatible additions, which a caller detects by the symbol
+int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows, nbmf_theta_hist: compatible additions, which a caller detects by the symbol
 // The sources this binary was compiled from: first 12 hex digits of the SHA-256 over nbmf_hip.hip, the *.inc files (sorted
 // by name) and include/nbmf_hip.h, put in by the Makefile (tools/src_hash.sh prints the same for the tree).  A profile or a
 // bench line that quotes it can be tied to a commit; a library built by hand without the Makefile says "unstamped".
@@ -3503,6 +3515,58 @@ int nbmf_score_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, do
   if (col_ll) HIPCHK(hipMemcpyAsync(col_ll, col_ll_d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   if (col_obs) HIPCHK(hipMemcpyAsync(col_obs, col_obs_d, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   if (want_cols) HIPCHK(hipStreamSynchronize(c->stream));
+  return NBMF_OK;
+}
+
+// ---- Theta counted against data: class histograms (nbmf_hist_kernels.inc) ----------------------------------
+// Per panel: the caller's data and mask rows up into staging panels (copy_rows), then the fused product-and-count kernel,
+// whose waves add onto an accumulator of 2 * bins + 2 integers that stays on the device for the whole call -- in
+// NBMF_HIST_COPIES copies (environment; default 64), which the finishing kernel adds up at the end -- and comes down once.
+// Integer adds: the panels need no alignment (a 16-row block that straddles two of them is formed twice, and each of
+// its rows counted in the panel that holds it).
+int nbmf_theta_hist(nbmf_ctx* c, int64_t row0, int64_t nrows, int bins, const uint8_t* x, int64_t ldx, const uint8_t* mask,
+                    int64_t ldmask, int64_t* hist, int64_t* nan_count) {
+  if (int rc = predict_ready(c)) return rc;
+  if (int rc = check_rows(c, row0, nrows)) return rc;
+  if (bins < 1 || bins > NBMF_HIST_MAX_BINS) return fail(NBMF_ERR_ARG, "bins must be in [1, %d] (got %d)", NBMF_HIST_MAX_BINS, bins);
+  if (ldx < c->n) return fail(NBMF_ERR_ARG, "ldx %lld is less than n = %lld", (long long)ldx, (long long)c->n);
+  if (mask && ldmask < c->n) return fail(NBMF_ERR_ARG, "ldmask %lld is less than n = %lld", (long long)ldmask, (long long)c->n);
+  if (!hist) return fail(NBMF_ERR_ARG, "null output");
+  if (nrows > 0 && !x) return fail(NBMF_ERR_ARG, "null data");
+  const size_t slots = 2 * (size_t)bins;
+  std::fill(hist, hist + slots, (int64_t)0);   // (nrows == 0: nothing is read; the counts over no rows)
+  if (nan_count) nan_count[0] = nan_count[1] = 0;
+  if (nrows == 0) return NBMF_OK;
+  if (int rc = set_device(c)) return rc;
+  const long long n = c->n, ldp = panel_ld(c);
+  RowPanels pl;
+  if (int rc = plan_row_panels(c, "nbmf_theta_hist", row0, nrows, (size_t)ldp * (mask ? 2 : 1), false, &pl)) return rc;
+  PredictStage st{c->stream, {}};
+  unsigned char *x_d = nullptr, *m_d = nullptr;
+  const int copies = (int)std::min<long long>(1024, std::max<long long>(1, env_int("NBMF_HIST_COPIES", 64)));
+  unsigned long long *total_d = nullptr, *sum_d = nullptr;
+  HIPCHK(st.get(&x_d, (size_t)pl.stage_rows() * ldp));
+  if (mask) HIPCHK(st.get(&m_d, (size_t)pl.stage_rows() * ldp));
+  HIPCHK(st.get(&total_d, sizeof(unsigned long long) * (slots + 2) * copies));
+  HIPCHK(st.get(&sum_d, sizeof(unsigned long long) * (slots + 2)));
+  HIPCHK(hipMemsetAsync(total_d, 0, sizeof(unsigned long long) * (slots + 2) * copies, c->stream));
+  for (long long p0 = row0, pn; p0 < pl.end; p0 += pn) {
+    pn = pl.rows_at(p0);
+    const size_t done = (size_t)(p0 - row0);
+    HIPCHK(copy_rows(x_d, ldp, x + done * ldx, ldx, n, pn, hipMemcpyHostToDevice, c->stream));
+    if (mask) HIPCHK(copy_rows(m_d, ldp, mask + done * ldmask, ldmask, n, pn, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_hist_panel(c, pl, p0, pn, bins, x_d, m_d, copies, total_d));
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
+  }
+  static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the counters come down as they are");
+  hipLaunchKernelGGL(theta_hist_finish_kernel, dim3((unsigned)((slots + 2 + 255) / 256)), dim3(256), 0, c->stream,
+                     (const unsigned long long*)total_d, copies, (int)(slots + 2), sum_d);
+  HIPCHK(hipGetLastError());
+  int64_t nan[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(hist, sum_d, sizeof(int64_t) * slots, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(nan, sum_d + slots, sizeof nan, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (nan_count) nan_count[0] = nan[0], nan_count[1] = nan[1];
   return NBMF_OK;
 }
 

@@ -9,13 +9,19 @@ that end in a synchronise (the library's predict calls do; NumPy's are synchrono
   (b) Theta for 8192 rows, as float64 and as bytes (> 0.5): Context.predict_rows against np.clip(W[:8192] @ H, 0, 1);
   (c) the top N columns of each of those 8192 rows, N = 10 and 100, with and without a 10 %-dense exclude:
       Context.top_n against the best route there was before it (predict_rows float64, then np.argpartition and a sort of
-      the N on the host) and against the pure host route (clip(W @ H), then the same selection).
+      the N on the host) and against the pure host route (clip(W @ H), then the same selection);
+  (d) the log-likelihood per row and per column of those rows: Context.score_rows against predict_rows plus NumPy;
+  (e) the class histograms of Theta over those rows (uint8 data, 90 % mask): Context.theta_hist at 256, 1024 and 1 bins and
+      without a mask, against predict_rows float64 plus np.bincount per class, and -- what the histograms are for --
+      against sklearn.metrics.roc_auc_score on the slab.  Once with the tool's factors (K = 64 uniform factors: Theta lies
+      in [0.37, 0.63], a few bins that every wave hits) and once with factors that spread Theta over [0, 1].
 
 The host legs are the comparison; the device path is never its own yardstick.  Before any time is taken the device and host
 results are compared at these sizes within tests/test_gpu_predict.py's bound, 2.1 K 2^-53 (|W| @ |H|) per entry; the
 ranking is compared exactly with the host selection over the device's own slab (the shape has no ties); the score sums are
 compared with the host's over the device's own slab within tests/test_gpu_score_samples.py's bound plus NumPy's own
-summation error.  ``--legs`` picks the legs to time (default: all four).
+summation error; the class histograms are compared for EQUALITY with NumPy's over the device's own slab.  ``--legs`` picks
+the legs to time (default: the first four; ``theta_hist`` is asked for by name).
 Prints progress lines and, last, ONE JSON line.  Needs an MI355X: there is no CPU fallback."""
 import argparse
 import json
@@ -34,10 +40,12 @@ ap.add_argument("--k", type=int, default=64)
 ap.add_argument("--pairs", type=int, default=1 << 22)
 ap.add_argument("--rows", type=int, default=8192)
 ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--legs", default="pairs,slabs,top_n,score_samples", help="comma-separated: pairs, slabs, top_n, score_samples")
+ap.add_argument("--legs", default="pairs,slabs,top_n,score_samples",
+                help="comma-separated: pairs, slabs, top_n, score_samples, theta_hist")
+ap.add_argument("--device-only", action="store_true", help="theta_hist: skip the host legs (for a kernel trace of the device legs)")
 args = ap.parse_args()
 legs = set(args.legs.split(","))
-assert legs <= {"pairs", "slabs", "top_n", "score_samples"}, f"unknown leg in {args.legs}"
+assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist"}, f"unknown leg in {args.legs}"
 m, n, k, P, R = args.m, args.n, args.k, args.pairs, min(args.rows, args.m)
 
 
@@ -203,5 +211,63 @@ with _hip.Context(m, n, k) as ctx:
         d["upload_share_estimated"] = min(1.0, 2.0 * max(0.0, d["device_s"] - d["device_no_mask_s"]) / d["device_s"])
         d["speedup_vs_predict_rows_then_host"] = d["predict_rows_then_host_s"] / d["device_s"]
         res["score_samples_leg"] = d
+
+    # ---- (e) class histograms of Theta ------------------------------------------------------------------------------------------
+    if "theta_hist" in legs:
+        gh = np.random.default_rng(2025)                    # (its own stream: the same data whichever legs ran before)
+        X = gh.random((R, n)) < 0.25
+        mask = gh.random((R, n)) < 0.90
+
+        def host_hist(bins, mk):
+            """predict_rows, then the contract on the host: one multiplication per entry, np.bincount per class."""
+            theta = ctx.predict_rows(0, R, out=out64)
+            obs = np.ones((R, n), dtype=bool) if mk is None else mk
+            b = np.minimum((theta * bins).astype(np.int64), bins - 1)
+            return np.stack([np.bincount(b[obs & ~X], minlength=bins), np.bincount(b[obs & X], minlength=bins)])
+
+        def host_auc():
+            from sklearn.metrics import roc_auc_score
+            theta = ctx.predict_rows(0, R, out=out64)
+            return roc_auc_score(X[mask], theta[mask])
+
+        def timed_legs(tag):
+            """Equality first, then the device legs (and, unless --device-only, the host legs) for the factors in ctx."""
+            from nbmf_mm_amd import _metrics
+            t = {}
+            for bins, mk in ((256, mask), (1024, mask), (1, mask), (1024, None)):
+                hist, nan_count = ctx.theta_hist(X, mk, 0, R, bins=bins)
+                assert np.array_equal(hist, host_hist(bins, mk)) and not nan_count.any(), \
+                    f"theta_hist ({tag}, bins = {bins}) disagrees with NumPy over predict_rows"
+            hist, _ = ctx.theta_hist(X, mask, 0, R, bins=1024)
+            t["bins_hit_1024"] = int(np.count_nonzero(hist.sum(0)))
+            t["auc_1024"], t["auc_slack_1024"] = _metrics.auc_from_hist(hist)
+            for name, bins, mk in (("device_256", 256, mask), ("device_1024", 1024, mask), ("device_1", 1, mask),
+                                   ("device_1024_no_mask", 1024, None)):
+                t[name + "_s"], t[name + "_all_s"] = median_s(lambda: ctx.theta_hist(X, mk, 0, R, bins=bins))
+                say(f"theta_hist {tag} {name}", t[name + "_s"])
+            if not args.device_only:
+                t["predict_rows_then_bincount_s"], t["predict_rows_then_bincount_all_s"] = median_s(lambda: host_hist(1024, mask))
+                say(f"{tag} predict_rows + np.bincount", t["predict_rows_then_bincount_s"])
+                exact = host_auc()
+                assert abs(exact - t["auc_1024"]) <= t["auc_slack_1024"] + 1e-15, "the binned AUC is outside its slack"
+                t["exact_auc"] = exact
+                t["predict_rows_then_sklearn_auc_s"], t["predict_rows_then_sklearn_auc_all_s"] = median_s(host_auc)
+                say(f"{tag} predict_rows + roc_auc_score", t["predict_rows_then_sklearn_auc_s"])
+                t["speedup_vs_predict_rows_then_bincount"] = t["predict_rows_then_bincount_s"] / t["device_1024_s"]
+                t["speedup_vs_predict_rows_then_sklearn_auc"] = t["predict_rows_then_sklearn_auc_s"] / t["device_1024_s"]
+            # with and without the mask differ by one of the two byte panels that cross PCIe: twice the difference estimates
+            # the upload's share of the call.  Derived from two end-to-end times, not a trace.
+            t["upload_share_estimated"] = min(1.0, 2.0 * max(0.0, t["device_1024_s"] - t["device_1024_no_mask_s"]) / t["device_1024_s"])
+            return t
+
+        e = {"data": "uint8", "observed": float(mask.mean()), "input_bytes": 2 * R * n, "output_bytes": 8 * (2 * 1024 + 2)}
+        e["concentrated"] = timed_legs("concentrated")
+        # factors that spread Theta over [0, 1]: each row of W leans on a few components, H is bimodal
+        W2 = gh.random((m, k)) ** 12
+        W2 /= W2.sum(1, keepdims=True)
+        H2 = np.where(gh.random((k, n)) < 0.5, gh.uniform(0.0, 0.2, (k, n)), gh.uniform(0.8, 1.0, (k, n)))
+        ctx.set_factors(np.ascontiguousarray(W2.T), H2)
+        e["spread"] = timed_legs("spread")
+        res["theta_hist_leg"] = e
 
 print(json.dumps(res))
