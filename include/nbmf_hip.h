@@ -295,6 +295,35 @@ int nbmf_theta_hist(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int bins,
                     const uint8_t* mask /* NULL: all observed; nonzero = observed */, int64_t ldmask,
                     int64_t* hist /* [2][bins]: class 0 first */, int64_t* nan_count /* [2], may be NULL */);
 
+/* Where given entries of Theta stand in the order nbmf_top_n ranks their row by: the position of held-out (row, column)
+ * entries among all n columns, at any depth, with a few integers per entry leaving the device instead of the row.  The
+ * TARGETS of row row0 + r are the columns indices[indptr[r] .. indptr[r + 1]) -- a CSR slice; indptr[0] may be greater than
+ * 0, so nrows + 1 entries of a larger CSR's indptr can be passed with its whole indices.  Targets of a row may come in any
+ * order and may repeat; each is answered on its own.  With theta[j] bit for bit the entry nbmf_predict_rows(..., clip_theta,
+ * NBMF_PREDICT_F64, ...) returns, a column j' is ELIGIBLE if theta[j'] is not NaN and it is not excluded (exclude as in
+ * nbmf_top_n: nrows x n bytes, leading dimension ldx >= n, nonzero = skipped, nothing beyond column n - 1 read), and
+ *   out_eligible[r] = the eligible columns of the row
+ * and for a target j at position p of indices that is eligible, over the eligible columns j' and comparing numerically
+ * (-0.0 equals +0.0),
+ *   out_above[p] = #{j' : theta[j'] > theta[j]},     out_tied[p] = #{j' != j : theta[j'] == theta[j]},
+ *   out_rank[p]  = out_above[p] + #{j' < j : theta[j'] == theta[j]},     out_scores[p] = theta[j]:
+ * out_rank is 0-based and is the slot nbmf_top_n puts column j in (the same order, tie rule and eligibility), for any
+ * depth, not only below NBMF_TOP_N_MAX.  A target that is itself excluded or NaN gets rank = above = tied = -1 and its
+ * theta as the score (NaN stays NaN; an excluded target still reports its theta).  The four per-target outputs are indexed
+ * like indices; positions outside [indptr[0], indptr[nrows]) are neither read nor written.  Any output may be NULL, not
+ * all five.  A row's results depend on that row, the factors, its exclude bytes and its targets only -- not on row0, on the
+ * panels (NBMF_PREDICT_PANEL_ROWS, as nbmf_predict_rows) or on other rows -- and the same call twice gives the same bits:
+ * the counts are integers (integer adds only, no floating-point atomics).  The cost of a row is ceil(targets / 8) passes
+ * over its n columns.  NBMF_ERR_ARG for rows outside [0, m), a NULL indptr, indptr[0] < 0 or a decreasing indptr, a NULL
+ * indices with targets present, a target column outside [0, n) (the message names the lowest offending position; indptr
+ * and the columns are checked on the host), ldx < n with an exclude, or all outputs NULL -- before anything is launched,
+ * and no output is touched then; nrows == 0 touches nothing.  Same state rules and synchronisation as nbmf_top_n. */
+int nbmf_rank_rows(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int clip_theta,
+                   const int64_t* indptr /* nrows + 1 */, const int32_t* indices,
+                   const uint8_t* exclude /* may be NULL */, int64_t ldx,
+                   int64_t* out_rank, int64_t* out_above, int64_t* out_tied, double* out_scores,
+                   int64_t* out_eligible /* nrows */);
+
 /* Multi-GPU, one process (and one context) per GPU.  The internal matrix Y is split over the ranks along
  *   shard_axis 0: its ROWS    -> W[:, rows] is local, H is replicated; each iteration all-reduces the k x n
  *                 H-step products [P1 | P2 | loglik] (2*K*N+1 doubles) before the H-update;

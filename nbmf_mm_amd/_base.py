@@ -9,8 +9,8 @@ from sklearn.base import BaseEstimator, TransformerMixin
 from sklearn.utils import check_array
 
 from . import _hip, _metrics
-from ._solver import (device_predict, device_score, device_score_samples, device_theta_hist, device_top_n, nbmf_mm_restarts,
-                      nbmf_mm_solver, w_only_transform)
+from ._solver import (device_predict, device_rank_of, device_score, device_score_samples, device_theta_hist, device_top_n,
+                      nbmf_mm_restarts, nbmf_mm_solver, w_only_transform)
 from ._utils import check_is_fitted
 
 # Accepted spellings of the two orientations: the exact strings of src/nbmf_mm/_base.py:127-137
@@ -239,15 +239,72 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         the device instead of ``n_features``: measured figures are in DESIGN.md 4.7 (profiles/top_n_on_device.txt)."""
         W, H = self._prediction_factors(W)
         n = _hip.top_n_count(n, name="n")
-        if exclude is not None:
-            if not hasattr(exclude, "toarray"):
-                exclude = np.asarray(exclude)
-            if exclude.dtype != np.bool_ and not np.issubdtype(exclude.dtype, np.number):
-                raise ValueError(f"exclude must be a bool or numeric matrix (got dtype {exclude.dtype})")
-            want = (W.shape[0], H.shape[1])
-            if exclude.ndim != 2 or tuple(exclude.shape) != want:
-                raise ValueError(f"exclude has shape {tuple(exclude.shape)}, the request describes {want}")
+        exclude = self._entry_matrix(exclude, "exclude", W, H)
         return device_top_n(W, H, n, exclude=exclude, device=self.device)
+
+    @staticmethod
+    def _entry_matrix(a, name, W, H):
+        """A matrix that marks entries of ``predict_proba(W)`` by its nonzeros (the ``exclude`` of :meth:`top_n`, the
+        ``targets`` of :meth:`rank_of`), validated without a device: dense (an ndarray is made of it) or scipy-sparse, of
+        a bool or numeric dtype and of shape ``(W.shape[0], n_features)``.  None passes through."""
+        if a is None:
+            return None
+        if not hasattr(a, "toarray"):
+            a = np.asarray(a)
+        if a.dtype != np.bool_ and not np.issubdtype(a.dtype, np.number):
+            raise ValueError(f"{name} must be a bool or numeric matrix (got dtype {a.dtype})")
+        want = (W.shape[0], H.shape[1])
+        if a.ndim != 2 or tuple(a.shape) != want:
+            raise ValueError(f"{name} has shape {tuple(a.shape)}, the request describes {want}")
+        return a
+
+    # -- how good the ranking is: where held-out entries stand in top_n's order (DESIGN.md 4.10) ----------------------------
+    def rank_of(self, targets, W=None, exclude=None):
+        """Where the entries marked by ``targets`` stand in the order :meth:`top_n` ranks their row by, counted on the GPU:
+        a :class:`~nbmf_mm_amd._metrics.Ranks` ``(rows, cols, rank, score, above, tied, eligible)``.  ``targets``: a dense
+        (bool or numeric) or scipy-sparse matrix of shape ``(W.shape[0], n_features)`` whose nonzero entries are the ones
+        to rank; ``rows`` / ``cols`` list them row by row, columns ascending.  ``exclude`` as in :meth:`top_n`.  Over the
+        ELIGIBLE features of its row (not excluded; ``eligible`` counts them per row), a target has ``above`` features
+        with a larger ``predict_proba(W)``, ``tied`` others with an equal one, and ``rank = above +`` the tied features
+        left of it: 0-based, exactly the slot :meth:`top_n` would show it in (``top_n(n, exclude=...)[0][i, rank] == col``
+        wherever ``rank < n``), but at any depth, not only the first 256.  ``score`` is the target's entry of
+        ``predict_proba(W)``.  A target that is itself excluded gets -1 / -1 / -1 and its score.  HELD-OUT USE:
+        ``fit(X_train)``, then ``rank_of(X_heldout, exclude=X_train)`` -- where do the ones the fit never saw land among
+        what the row does not have yet?  :meth:`ranking_metrics` turns the answer into recall@k, NDCG@k, MRR, mean
+        percentile rank and per-row AUC.  The cost of a row is one pass over its features per 8 targets, and a few integers
+        per target leave the device instead of the row."""
+        W, H = self._prediction_factors(W)
+        targets = self._entry_matrix(targets, "targets", W, H)
+        if targets is None:
+            raise ValueError("targets must be a matrix whose nonzero entries are the ones to rank (got None)")
+        exclude = self._entry_matrix(exclude, "exclude", W, H)
+        m = W.shape[0]
+        if hasattr(targets, "toarray"):                       # canonical CSR: no stored zeros, no repeats, columns ascending
+            t = (targets != 0).tocsr()
+            t.sum_duplicates()
+            t.eliminate_zeros()
+            t.sort_indices()
+            indptr, cols = t.indptr, t.indices
+            rows = np.repeat(np.arange(m, dtype=np.int64), np.diff(indptr))
+        else:
+            rows, cols = np.nonzero(targets)                  # row by row, columns ascending
+            indptr = np.concatenate(([0], np.cumsum(np.bincount(rows, minlength=m))))
+        indptr, indices = _hip.csr_targets(indptr, cols, m, H.shape[1])
+        rank, above, tied, score, eligible = device_rank_of(W, H, (indptr, indices), exclude=exclude, device=self.device)
+        return _metrics.Ranks(np.asarray(rows, dtype=np.int64), indices.astype(np.int64), rank, score, above, tied, eligible)
+
+    def ranking_metrics(self, X_heldout, exclude=None, W=None, k=10):
+        """The ranking metrics of the held-out entries ``X_heldout`` (its nonzeros, as the ``targets`` of :meth:`rank_of`)
+        under ``predict_proba(W)``: the dict of ``_metrics.ranking_from_ranks`` -- ``rows_scored``, ``hit_rate@k``,
+        ``recall@k``, ``precision@k``, ``ndcg@k``, ``mrr``, ``mean_percentile_rank`` and ``auc`` (the mean per-row ROC AUC).
+        HELD-OUT USE: ``fit(X_train)``, then ``ranking_metrics(X_heldout, exclude=X_train)``: the entries the fit saw are
+        left out of every ranking, as ``top_n(exclude=X_train)`` leaves them out of the recommendations.  The ``@k``
+        metrics and ``mrr`` judge the list :meth:`top_n` would show (ties go to the lower feature); ``auc`` and
+        ``mean_percentile_rank`` count a tie one half.  ``k`` is any positive integer -- it is not bounded by the 256 slots
+        of :meth:`top_n`.  Rows without an eligible held-out entry enter no mean."""
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError(f"k must be a positive integer (got {k!r})")
+        return _metrics.ranking_from_ranks(self.rank_of(X_heldout, W=W, exclude=exclude), k=int(k))
 
     def impute(self, X, mask):
         """A float64 copy of ``X`` in which every entry with ``mask == 0`` is replaced by ``predict_proba`` at exactly

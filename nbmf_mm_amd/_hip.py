@@ -38,6 +38,7 @@ SYMBOLS = [
     "nbmf_set_exchange_panels", "nbmf_set_peer_timeout_ms", "nbmf_run_batch", "nbmf_batch_stats", "nbmf_sweep_info",
     "nbmf_upload_v", "nbmf_selftest_mfma_peak", "nbmf_engine_stats", "nbmf_source_hash", "nbmf_comm_info", "nbmf_cancel", "nbmf_variant_stats", "nbmf_device_bus_id",
     "nbmf_predict_at", "nbmf_predict_rows", "nbmf_top_n", "nbmf_score_rows", "nbmf_theta_hist",
+    "nbmf_rank_rows",
 ]
 DATA_F64, DATA_U8, DATA_F32 = 0, 1, 2
 PREDICT_F64, PREDICT_U8 = 0, 1
@@ -180,6 +181,8 @@ def load():
     lib.nbmf_score_rows.argtypes = [c_void_p, c_int64, c_int64, c_int, c_double, c_void_p, c_int, c_int64, c_void_p, c_int64,
                                     c_void_p, c_void_p, c_void_p, c_void_p]
     lib.nbmf_theta_hist.argtypes = [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]
+    lib.nbmf_rank_rows.argtypes = [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p]
     for name in SYMBOLS:
         if name not in ("nbmf_last_error", "nbmf_source_hash"):
             getattr(lib, name).restype = c_int
@@ -272,6 +275,42 @@ def hist_bins(bins, name="bins"):
     if not 1 <= int(bins) <= HIST_MAX_BINS:
         raise ValueError(f"{name} must be in [1, {HIST_MAX_BINS}] (got {int(bins)})")
     return int(bins)
+
+
+def csr_targets(indptr, indices, nrows, n):
+    """The targets of ``rank_of`` as the library takes them -- ``(indptr, indices)``, C-contiguous int64 and int32 -- after
+    the checks that need no device: both integer-typed and 1-D, ``indptr`` of length ``nrows + 1``, non-negative and
+    non-decreasing (``indptr[0]`` may be above 0: a slice of a larger CSR's ``indptr`` goes with its whole ``indices``),
+    ``indices`` at least ``indptr[-1]`` long and every column at a position in ``[indptr[0], indptr[-1])`` inside
+    ``[0, n)``.  Raises ``ValueError`` otherwise, naming the lowest offending position."""
+    indptr, indices = np.asarray(indptr), np.asarray(indices)
+    for name, a in (("indptr", indptr), ("indices", indices)):
+        if not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"{name} must be an integer array (got dtype {a.dtype})")
+        if a.ndim != 1:
+            raise ValueError(f"{name} must be 1-D (got shape {a.shape})")
+    if indptr.size != nrows + 1:
+        raise ValueError(f"indptr must have nrows + 1 = {nrows + 1} entries (got {indptr.size})")
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    if indptr[0] < 0:
+        raise ValueError(f"indptr[0] = {int(indptr[0])} is negative")
+    down = np.flatnonzero(indptr[1:] < indptr[:-1])
+    if down.size:
+        r = int(down[0])
+        raise ValueError(f"indptr decreases at row {r} ({int(indptr[r + 1])} after {int(indptr[r])})")
+    first, last = int(indptr[0]), int(indptr[-1])
+    if indices.size < last:
+        raise ValueError(f"indices has {indices.size} entries, indptr describes {last}")
+    live = indices[first:last]
+    bad = np.flatnonzero((live < 0) | (live >= min(int(n), 2 ** 31)))
+    if bad.size:
+        p = first + int(bad[0])
+        raise ValueError(f"target column {int(indices[p])} at position {p} is outside [0, {int(n)})")
+    if indices.dtype != np.int32:               # (the positions outside [first, last) are never read: they go as zeros)
+        narrow = np.zeros(indices.size, dtype=np.int32)
+        narrow[first:last] = live
+        indices = narrow
+    return indptr, np.ascontiguousarray(indices)
 
 
 #: the dtypes a row array may have: one byte per entry (passed to the library as uint8), or float64
@@ -581,6 +620,33 @@ class Context:
         _check(self._lib.nbmf_theta_hist(self._h, row0, nrows, bins, x.ctypes.data_as(c_void_p), ldx, mptr, ldm,
                                          hist.ctypes.data_as(c_void_p), nan_count.ctypes.data_as(c_void_p)))
         return hist, nan_count
+
+    def rank_of(self, indptr, indices, row0=0, nrows=None, exclude=None, clip_theta=True):
+        """Where given columns stand in the order :meth:`top_n` ranks their row by, counted on the device
+        (``nbmf_rank_rows``): ``(rank, above, tied, scores, eligible)``.  The TARGETS of row ``row0 + r`` are the columns
+        ``indices[indptr[r]:indptr[r + 1]]`` (a CSR slice; ``indptr[0]`` may be above 0), in any order, repeats allowed.
+        The first four arrays are indexed like ``indices`` and ``indptr[-1]`` long (int64, ``scores`` float64); positions
+        below ``indptr[0]`` hold -1 / NaN.  ``eligible`` (int64, ``nrows``) counts the columns of the row that are neither
+        NaN nor excluded.  Over those columns, for a target j that is one of them: ``above`` columns have a larger Theta,
+        ``tied`` other columns an equal one, and ``rank = above +`` the tied columns left of j -- 0-based, the slot
+        :meth:`top_n` would put j in, at any depth.  ``scores`` is Theta at the target, bit for bit the entry
+        :meth:`predict_rows` returns.  A target that is itself excluded or NaN gets -1 / -1 / -1 and its Theta.
+        ``exclude`` as in :meth:`top_n`.  The cost of a row is ``ceil(targets / 8)`` passes over its n columns; only a few
+        integers per target come back from the device."""
+        row0, nrows = self._rows(row0, nrows)
+        indptr, indices = csr_targets(indptr, indices, nrows, self.n)
+        xptr, ldx = None, 0
+        if exclude is not None:
+            exclude, _, ldx = row_array(exclude, nrows, self.n, "exclude", BYTE_KINDS)
+            xptr = exclude.ctypes.data_as(c_void_p)
+        count = int(indptr[-1])
+        rank, above, tied = (np.full(count, -1, dtype=np.int64) for _ in range(3))
+        scores = np.full(count, np.nan)
+        eligible = np.empty(nrows, dtype=np.int64)
+        ptr = lambda a: a.ctypes.data_as(c_void_p)   # noqa: E731
+        _check(self._lib.nbmf_rank_rows(self._h, row0, nrows, int(bool(clip_theta)), ptr(indptr), ptr(indices), xptr, ldx,
+                                        ptr(rank), ptr(above), ptr(tied), ptr(scores), ptr(eligible)))
+        return rank, above, tied, scores, eligible
 
     def comm_init(self, uid: bytes, nranks: int, rank: int, shard_axis: int = 0):
         """Attach an RCCL communicator; shard_axis 0 = rows of the internal Y are split, 1 = columns."""

@@ -1,6 +1,10 @@
 """ROC AUC and calibration from the two class histograms of Theta (``Context.theta_hist``, ``NBMF.theta_histogram``): pure
 NumPy on ``2 * bins`` integers, no device.  ``hist`` is int64 of shape ``(2, bins)``: ``hist[0, b]`` the observed zeros and
-``hist[1, b]`` the observed ones whose Theta lies in bin b, ``[b / bins, (b + 1) / bins)`` (the last bin closed at 1)."""
+``hist[1, b]`` the observed ones whose Theta lies in bin b, ``[b / bins, (b + 1) / bins)`` (the last bin closed at 1).
+And the ranking metrics of held-out entries from their positions in ``top_n``'s order (``Context.rank_of``,
+``NBMF.rank_of``): pure NumPy on a few integers per entry (:class:`Ranks`, :func:`ranking_from_ranks`)."""
+from collections import namedtuple
+
 import numpy as np
 
 
@@ -67,3 +71,86 @@ def calibration_from_hist(hist, n_bins):
         prob_pred[q] = odd / (2 * bins * int(counts[q]))
     return prob_true, prob_pred, counts
 
+
+#: What ``NBMF.rank_of`` returns.  ``rows`` / ``cols`` are the targets in CSR order (row ascending); ``rank``, ``score``,
+#: ``above`` and ``tied`` belong to them one to one (``Context.rank_of``); ``eligible`` is per row of the request.
+Ranks = namedtuple("Ranks", ["rows", "cols", "rank", "score", "above", "tied", "eligible"])
+
+
+def _mean(values):
+    return float(np.mean(values)) if len(values) else float("nan")
+
+
+def ranking_from_ranks(ranks, k=10):
+    """The ranking metrics of the targets in ``ranks`` (:class:`Ranks`) -- the held-out ones of each row -- as a dict.
+    ``P_i`` is the number of eligible targets of row i (``rank >= 0``: neither excluded nor NaN), ``E_i = eligible[i]``;
+    rows with ``P_i = 0`` enter no mean.
+
+        rows_scored           the rows with P_i > 0
+        hit_rate@k            the share of them with a target at rank < k
+        recall@k              mean of #{rank < k} / P_i
+        precision@k           mean of #{rank < k} / k
+        ndcg@k                mean of sum_{rank < k} 1 / log2(rank + 2)  over  sum_{s < min(P_i, k)} 1 / log2(s + 2)
+        mrr                   mean of 1 / (the row's smallest rank + 1)
+        mean_percentile_rank  over ALL eligible targets, pooled: (above + tied / 2) / (E_i - 1), 0 where E_i = 1
+        auc                   mean over the rows with 0 < P_i < E_i of the ROC AUC of the row's eligible columns, targets
+                              against the rest, ties counted one half
+
+    The ``@k`` metrics and ``mrr`` use ``rank``: the slot ``top_n`` would show the target in, ties broken towards the lower
+    column.  ``mean_percentile_rank`` and ``auc`` use MID-RANKS: a tie counts one half, whatever the columns.  The AUC of a
+    row is ``1 - sum_t (neg_above_t + neg_tied_t / 2) / (P_i (E_i - P_i))`` with ``neg_above_t`` / ``neg_tied_t`` the
+    ``above`` / ``tied`` of target t less the row's own eligible targets above, respectively tied with, t, which are found
+    here from the targets' ``score`` compared numerically; the sums are formed in integers and divided once.  ``k`` is any
+    positive integer.  A mean over nothing is NaN.  A target listed twice in a row is an error (``ValueError``): every
+    metric here counts entries, not mentions."""
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError(f"k must be a positive integer (got {k!r})")
+    k = int(k)
+    per_target = (ranks.rows, ranks.cols, ranks.rank, ranks.above, ranks.tied)
+    rows, cols, rank, above, tied = (np.asarray(a, dtype=np.int64) for a in per_target)
+    score = np.asarray(ranks.score, dtype=np.float64)
+    E = np.asarray(ranks.eligible, dtype=np.int64)
+    if len({a.shape for a in (rows, cols, rank, above, tied, score)}) != 1 or rows.ndim != 1 or E.ndim != 1:
+        raise ValueError("the per-target arrays of ranks must be 1-D and equally long, eligible 1-D")
+    m = E.size
+    if rows.size and (rows.min() < 0 or rows.max() >= m or np.any(rows[1:] < rows[:-1])):
+        raise ValueError("ranks.rows must ascend inside [0, len(eligible))")
+    order = np.lexsort((cols, rows))
+    if np.any((rows[order][1:] == rows[order][:-1]) & (cols[order][1:] == cols[order][:-1])):
+        raise ValueError("a target is listed twice in a row")
+    ok = rank >= 0
+    r, rk, ab, td, sc = rows[ok], rank[ok], above[ok], tied[ok], score[ok]
+    P = np.bincount(r, minlength=m)
+    scored = P > 0
+    out = {"rows_scored": int(scored.sum())}
+    top = rk < k
+    hits = np.bincount(r[top], minlength=m)
+    out[f"hit_rate@{k}"] = _mean(hits[scored] > 0)
+    out[f"recall@{k}"] = _mean(hits[scored] / P[scored])
+    out[f"precision@{k}"] = _mean(hits[scored] / k)
+    dcg = np.zeros(m)
+    np.add.at(dcg, r[top], 1.0 / np.log2(rk[top] + 2.0))
+    ideal = np.concatenate(([0.0], np.cumsum(1.0 / np.log2(np.arange(min(k, int(P.max()) if m else 0)) + 2.0))))
+    out[f"ndcg@{k}"] = _mean(dcg[scored] / ideal[np.minimum(P[scored], k)])
+    best = np.full(m, np.iinfo(np.int64).max)
+    np.minimum.at(best, r, rk)
+    out["mrr"] = _mean(1.0 / (best[scored] + 1.0))
+    Et = E[r]
+    out["mean_percentile_rank"] = _mean(np.where(Et > 1, (ab + td / 2.0) / np.maximum(Et - 1, 1), 0.0))
+    # the row's own targets above / tied with each target: sort them by (row, score) and read the runs of equal scores
+    by = np.lexsort((sc, r))
+    rs, ss = r[by], sc[by]
+    new_run = np.ones(rs.size, dtype=bool)
+    new_run[1:] = (rs[1:] != rs[:-1]) | (ss[1:] != ss[:-1])
+    run = np.cumsum(new_run) - 1
+    start = np.flatnonzero(new_run)
+    length = np.diff(np.append(start, rs.size))
+    row_end = np.cumsum(P)[rs]                       # one past the row's last target in the sorted order
+    own_above = row_end - (start + length)[run]
+    own_tied = length[run] - 1
+    twice = np.zeros(m, dtype=np.int64)              # 2 neg_above + neg_tied, summed per row: exact
+    np.add.at(twice, rs, 2 * (ab[by] - own_above) + (td[by] - own_tied))
+    both = scored & (P < E)
+    pairs = (P[both] * (E[both] - P[both])).astype(np.float64)
+    out["auc"] = _mean(1.0 - twice[both] / (2.0 * pairs))
+    return out

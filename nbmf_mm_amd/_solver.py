@@ -303,6 +303,36 @@ def device_top_n(W, H, top, exclude=None, device=0):
         return cols, scores
 
 
+def device_rank_of(W, H, targets_csr, exclude=None, device=0):
+    """Where the target features of every row of ``W`` stand in the order :func:`device_top_n` ranks the row by, counted on
+    the GPU (``Context.rank_of``): ``(rank, above, tied, scores, eligible)``, the first four indexed like the targets'
+    ``indices``, ``eligible`` per row.  ``W``, ``H`` as in :func:`device_predict`; ``targets_csr`` the ``(indptr, indices)``
+    of a CSR pattern with ``W.shape[0]`` rows, already validated (``_hip.csr_targets``); ``exclude`` as in
+    :func:`device_top_n`, made dense one row block of at most ``TOP_N_EXCLUDE_BLOCK_BYTES`` at a time -- a block passes its
+    slice of ``indptr`` and the whole ``indices``, and a row's result does not depend on the blocks.  Factors only: no data
+    is uploaded."""
+    indptr, indices = targets_csr
+    if hasattr(exclude, "toarray"):
+        exclude = exclude.tocsr()
+    with _factors_only(W, H, device) as (ctx, m, n):
+        if exclude is None:
+            return ctx.rank_of(indptr, indices, 0, m, clip_theta=True)
+        count = int(indptr[-1])
+        rank, above, tied = (np.full(count, -1, dtype=np.int64) for _ in range(3))
+        scores = np.full(count, np.nan)
+        eligible = np.empty(m, dtype=np.int64)
+        block = max(1, min(m, TOP_N_EXCLUDE_BLOCK_BYTES // max(n, 1)))
+        for r0 in range(0, m, block):
+            nr = min(block, m - r0)
+            x = _row_block(exclude, r0, nr, True)
+            got = ctx.rank_of(indptr[r0:r0 + nr + 1], indices, r0, nr, exclude=x, clip_theta=True)
+            t = slice(int(indptr[r0]), int(indptr[r0 + nr]))
+            for whole, part in zip((rank, above, tied, scores), got):
+                whole[t] = part[t]
+            eligible[r0:r0 + nr] = got[4]
+        return rank, above, tied, scores, eligible
+
+
 #: bytes of data (and as many of mask) that :func:`device_score_samples` converts or makes dense at a time (one row block)
 SCORE_SAMPLES_BLOCK_BYTES = 64 << 20
 

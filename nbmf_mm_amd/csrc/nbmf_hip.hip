@@ -322,6 +322,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 #include "nbmf_predict_kernels.inc"
 #include "nbmf_score_kernels.inc"
 #include "nbmf_hist_kernels.inc"
+#include "nbmf_rank_kernels.inc"
 
 }  // namespace
 
@@ -2478,8 +2479,8 @@ int one_shot(nbmf_ctx* c, bool with_prior, int strict, int clip, bool collect_ti
 // (also the single-launch engine's end-of-run guard: small_guard)
 int loss_by_launches(nbmf_ctx* c, double* loss) { return one_shot(c, /*with_prior=*/true, 0, 0, /*collect_timing=*/true, loss); }
 
-// ---- shared by the five entry points that read Theta back: nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows,
-// nbmf_theta_hist
+// ---- shared by the six entry points that read Theta back: nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows,
+// nbmf_theta_hist, nbmf_rank_rows
 // (DESIGN.md 4.6).  Staging of one such call, from the pool: given back when the call returns, on every path, after the
 // stream has drained (a pooled block may be handed to the next caller at once).
 struct PredictStage {
@@ -2498,7 +2499,7 @@ struct PredictStage {
   }
 };
 
-// The checks all five share, in the order the header gives them: factors, not data (so not ready()).
+// The checks all six share, in the order the header gives them: factors, not data (so not ready()).
 int predict_ready(nbmf_ctx* c) {
   if (!c) return fail(NBMF_ERR_ARG, "null context");
   if (!c->have_factors) return fail(NBMF_ERR_STATE, "no factors on the device");
@@ -2506,7 +2507,7 @@ int predict_ready(nbmf_ctx* c) {
   return NBMF_OK;
 }
 
-int check_rows(nbmf_ctx* c, int64_t row0, int64_t nrows) {   // the four row-slab entry points: all but nbmf_predict_at
+int check_rows(nbmf_ctx* c, int64_t row0, int64_t nrows) {   // the five row-slab entry points: all but nbmf_predict_at
   if (nrows < 0 || row0 < 0 || row0 > c->m || nrows > c->m - row0)
     return fail(NBMF_ERR_ARG, "rows [%lld, %lld + %lld) are not inside [0, %lld)", (long long)row0, (long long)row0, (long long)nrows,
                 (long long)c->m);
@@ -2584,7 +2585,7 @@ hipError_t launch_hist_panel(nbmf_ctx* c, const RowPanels& pl, long long p0, lon
 // ------------------------------------------------------------------------------------------
 extern "C" {
 
-int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows, nbmf_theta_hist: compatible additions, which a caller detects by the symbol
+int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows, nbmf_theta_hist, nbmf_rank_rows: compatible additions, which a caller detects by the symbol
 // The sources this binary was compiled from: first 12 hex digits of the SHA-256 over nbmf_hip.hip, the *.inc files (sorted
 // by name) and include/nbmf_hip.h, put in by the Makefile (tools/src_hash.sh prints the same for the tree).  A profile or a
 // bench line that quotes it can be tied to a commit; a library built by hand without the Makefile says "unstamped".
@@ -3567,6 +3568,82 @@ int nbmf_theta_hist(nbmf_ctx* c, int64_t row0, int64_t nrows, int bins, const ui
   HIPCHK(hipMemcpyAsync(nan, sum_d + slots, sizeof nan, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (nan_count) nan_count[0] = nan[0], nan_count[1] = nan[1];
+  return NBMF_OK;
+}
+
+// ---- Theta ranked at given entries: where held-out columns stand in top_n's order (nbmf_rank_kernels.inc) ---
+// Per panel: the product kernel of nbmf_predict_rows, unchanged, into the staging panel (as nbmf_top_n: a score is bit for
+// bit the entry nbmf_predict_rows returns), the panel's slice of indptr and its range of indices up, the counting kernel,
+// and the same range of every output that was asked for back: a few integers per target instead of n doubles per row.
+// The target staging holds the most targets any one panel has, found from indptr before the loop.
+int nbmf_rank_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, const int64_t* indptr, const int32_t* indices,
+                   const uint8_t* exclude, int64_t ldx, int64_t* out_rank, int64_t* out_above, int64_t* out_tied, double* out_scores,
+                   int64_t* out_eligible) {
+  if (int rc = predict_ready(c)) return rc;
+  if (int rc = check_rows(c, row0, nrows)) return rc;
+  if (exclude && ldx < c->n) return fail(NBMF_ERR_ARG, "ldx %lld is less than n = %lld", (long long)ldx, (long long)c->n);
+  if (nrows == 0) return NBMF_OK;
+  if (!out_rank && !out_above && !out_tied && !out_scores && !out_eligible) return fail(NBMF_ERR_ARG, "no output requested");
+  if (!indptr) return fail(NBMF_ERR_ARG, "null indptr");
+  if (indptr[0] < 0) return fail(NBMF_ERR_ARG, "indptr[0] = %lld is negative", (long long)indptr[0]);
+  for (int64_t r = 0; r < nrows; ++r)
+    if (indptr[r + 1] < indptr[r])
+      return fail(NBMF_ERR_ARG, "indptr decreases at row %lld (%lld after %lld)", (long long)(row0 + r), (long long)indptr[r + 1],
+                  (long long)indptr[r]);
+  const long long n = c->n;
+  const int64_t first = indptr[0], last = indptr[nrows];
+  if (last > first && !indices) return fail(NBMF_ERR_ARG, "null indices");
+  for (int64_t p = first; p < last; ++p)
+    if (indices[p] < 0 || indices[p] >= n)
+      return fail(NBMF_ERR_ARG, "target column %d at position %lld is outside [0, %lld)", (int)indices[p], (long long)p, n);
+  if (int rc = set_device(c)) return rc;
+  RowPanels pl;   // (the panel of nbmf_predict_rows, float64)
+  if (int rc = plan_row_panels(c, "nbmf_rank_rows", row0, nrows, (size_t)panel_ld(c) * sizeof(double), false, &pl)) return rc;
+  long long most = 1;   // targets of the fullest panel (1: no empty staging block)
+  for (long long p0 = row0, pn; p0 < pl.end; p0 += pn) {
+    pn = pl.rows_at(p0);
+    most = std::max<long long>(most, indptr[p0 - row0 + pn] - indptr[p0 - row0]);
+  }
+  static_assert(sizeof(int64_t) == sizeof(long long), "indptr and the integer outputs travel as they are");
+  const size_t rows = (size_t)pl.stage_rows();
+  PredictStage st{c->stream, {}};
+  double *panel_d = nullptr, *scores_d = nullptr;
+  long long *indptr_d = nullptr, *rank_d = nullptr, *above_d = nullptr, *tied_d = nullptr, *elig_d = nullptr;
+  int* indices_d = nullptr;
+  unsigned char* ex_d = nullptr;
+  HIPCHK(st.get(&panel_d, sizeof(double) * rows * pl.ldp));
+  HIPCHK(st.get(&indptr_d, sizeof(long long) * (rows + 1)));
+  HIPCHK(st.get(&indices_d, sizeof(int) * (size_t)most));
+  if (out_rank) HIPCHK(st.get(&rank_d, sizeof(long long) * (size_t)most));
+  if (out_above) HIPCHK(st.get(&above_d, sizeof(long long) * (size_t)most));
+  if (out_tied) HIPCHK(st.get(&tied_d, sizeof(long long) * (size_t)most));
+  if (out_scores) HIPCHK(st.get(&scores_d, sizeof(double) * (size_t)most));
+  if (out_eligible) HIPCHK(st.get(&elig_d, sizeof(long long) * rows));
+  if (exclude) HIPCHK(st.get(&ex_d, rows * n));
+  for (long long p0 = row0, pn; p0 < pl.end; p0 += pn) {
+    pn = pl.rows_at(p0);
+    const size_t done = (size_t)(p0 - row0);
+    const long long base = indptr[done];
+    const size_t cnt = (size_t)(indptr[done + pn] - base);   // <= most
+    if (exclude) HIPCHK(copy_rows(ex_d, n, exclude + done * ldx, ldx, n, pn, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(indptr_d, indptr + done, sizeof(long long) * (size_t)(pn + 1), hipMemcpyHostToDevice, c->stream));
+    if (cnt) HIPCHK(hipMemcpyAsync(indices_d, indices + base, sizeof(int) * cnt, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_theta_panel(c, pl, p0, pn, NBMF_PREDICT_F64, clip_theta, 0.0, panel_d));
+    hipLaunchKernelGGL(rank_rows_kernel, dim3((unsigned)pn), dim3(RK_THREADS), 0, c->stream, (const double*)panel_d, pl.ldp, n,
+                       (const unsigned char*)ex_d, n, (const long long*)indptr_d, (const int*)indices_d, base, rank_d, above_d,
+                       tied_d, scores_d, elig_d);
+    HIPCHK(hipGetLastError());
+    if (cnt) {
+      const size_t w64 = sizeof(int64_t) * cnt;
+      if (out_rank) HIPCHK(hipMemcpyAsync(out_rank + base, rank_d, w64, hipMemcpyDeviceToHost, c->stream));
+      if (out_above) HIPCHK(hipMemcpyAsync(out_above + base, above_d, w64, hipMemcpyDeviceToHost, c->stream));
+      if (out_tied) HIPCHK(hipMemcpyAsync(out_tied + base, tied_d, w64, hipMemcpyDeviceToHost, c->stream));
+      if (out_scores) HIPCHK(hipMemcpyAsync(out_scores + base, scores_d, sizeof(double) * cnt, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (out_eligible)
+      HIPCHK(hipMemcpyAsync(out_eligible + done, elig_d, sizeof(int64_t) * (size_t)pn, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
+  }
   return NBMF_OK;
 }
 

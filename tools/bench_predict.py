@@ -14,14 +14,18 @@ that end in a synchronise (the library's predict calls do; NumPy's are synchrono
   (e) the class histograms of Theta over those rows (uint8 data, 90 % mask): Context.theta_hist at 256, 1024 and 1 bins and
       without a mask, against predict_rows float64 plus np.bincount per class, and -- what the histograms are for --
       against sklearn.metrics.roc_auc_score on the slab.  Once with the tool's factors (K = 64 uniform factors: Theta lies
-      in [0.37, 0.63], a few bins that every wave hits) and once with factors that spread Theta over [0, 1].
+      in [0.37, 0.63], a few bins that every wave hits) and once with factors that spread Theta over [0, 1];
+  (f) where held-out entries of those rows stand in top_n's order: Context.rank_of with 10 targets per row under a
+      10 %-dense exclude and with 100 targets per row, against predict_rows float64 plus NumPy rank counting (compares of
+      the whole slab per target slot, or one sort of every row and binary searches, whichever is faster), with top_n(10)
+      under the same exclude beside it for orientation.
 
 The host legs are the comparison; the device path is never its own yardstick.  Before any time is taken the device and host
 results are compared at these sizes within tests/test_gpu_predict.py's bound, 2.1 K 2^-53 (|W| @ |H|) per entry; the
 ranking is compared exactly with the host selection over the device's own slab (the shape has no ties); the score sums are
 compared with the host's over the device's own slab within tests/test_gpu_score_samples.py's bound plus NumPy's own
-summation error; the class histograms are compared for EQUALITY with NumPy's over the device's own slab.  ``--legs`` picks
-the legs to time (default: the first four; ``theta_hist`` is asked for by name).
+summation error; the class histograms and the ranks are compared for EQUALITY with NumPy's over the device's own slab.
+``--legs`` picks the legs to time (default: the first four; ``theta_hist`` and ``rank_of`` are asked for by name).
 Prints progress lines and, last, ONE JSON line.  Needs an MI355X: there is no CPU fallback."""
 import argparse
 import json
@@ -41,11 +45,12 @@ ap.add_argument("--pairs", type=int, default=1 << 22)
 ap.add_argument("--rows", type=int, default=8192)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--legs", default="pairs,slabs,top_n,score_samples",
-                help="comma-separated: pairs, slabs, top_n, score_samples, theta_hist")
-ap.add_argument("--device-only", action="store_true", help="theta_hist: skip the host legs (for a kernel trace of the device legs)")
+                help="comma-separated: pairs, slabs, top_n, score_samples, theta_hist, rank_of")
+ap.add_argument("--device-only", action="store_true",
+                help="theta_hist, rank_of: skip the timed host legs (for a kernel trace of the device legs)")
 args = ap.parse_args()
 legs = set(args.legs.split(","))
-assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist"}, f"unknown leg in {args.legs}"
+assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist", "rank_of"}, f"unknown leg in {args.legs}"
 m, n, k, P, R = args.m, args.n, args.k, args.pairs, min(args.rows, args.m)
 
 
@@ -211,6 +216,79 @@ with _hip.Context(m, n, k) as ctx:
         d["upload_share_estimated"] = min(1.0, 2.0 * max(0.0, d["device_s"] - d["device_no_mask_s"]) / d["device_s"])
         d["speedup_vs_predict_rows_then_host"] = d["predict_rows_then_host_s"] / d["device_s"]
         res["score_samples_leg"] = d
+
+    # ---- (f) ranks of held-out entries (before (e), which changes the factors) ---------------------------------------------------
+    if "rank_of" in legs:
+        gr = np.random.default_rng(2026)                    # (its own stream: the same data whichever legs ran before)
+        excl = gr.random((R, n)) < 0.10
+
+        def host_by_compares(theta, tcols, ex):
+            """Per target slot three compares of the whole slab: rows x targets x n of them."""
+            ok = ~np.isnan(theta) if ex is None else ~np.isnan(theta) & ~ex
+            col = np.arange(n)[None, :]
+            out = np.empty((3,) + tcols.shape, dtype=np.int64)
+            for q in range(tcols.shape[1]):
+                j = tcols[:, q:q + 1]
+                v = np.take_along_axis(theta, j, axis=1)
+                same = ok & (theta == v)
+                out[1, :, q] = (ok & (theta > v)).sum(1)
+                out[2, :, q] = same.sum(1) - 1
+                out[0, :, q] = out[1, :, q] + (same & (col < j)).sum(1)
+            out[:, ~np.take_along_axis(ok, tcols, axis=1)] = -1
+            return out[0], out[1], out[2], ok.sum(1)
+
+        def host_by_sort(theta, tcols, ex):
+            """One sort of every row's eligible entries, then two binary searches per target; ties are settled by a scan
+            of the row, only where there are any."""
+            ok = ~np.isnan(theta) if ex is None else ~np.isnan(theta) & ~ex
+            E = ok.sum(1)
+            srt = np.sort(np.where(ok, theta, np.nan), axis=1)          # NaN last: the first E of a row are the eligible
+            out = np.empty((3,) + tcols.shape, dtype=np.int64)
+            for i in range(theta.shape[0]):
+                v = theta[i, tcols[i]]
+                lo, hi = np.searchsorted(srt[i, :E[i]], v, "left"), np.searchsorted(srt[i, :E[i]], v, "right")
+                out[1, i], out[2, i] = E[i] - hi, hi - lo - 1
+                out[0, i] = out[1, i]
+                for q in np.flatnonzero(out[2, i] > 0):
+                    j = tcols[i, q]
+                    out[0, i, q] += np.count_nonzero(ok[i, :j] & (theta[i, :j] == v[q]))
+            out[:, ~np.take_along_axis(ok, tcols, axis=1)] = -1
+            return out[0], out[1], out[2], E
+
+        f = {"exclude_density": float(excl.mean())}
+        for T, ex in ((10, excl), (100, None)):
+            # T distinct columns per row, one from each of T stripes, in shuffled order
+            tcols = gr.permuted(gr.integers(0, n // T, (R, T)) + np.arange(T) * (n // T), axis=1).astype(np.int32)
+            indptr, indices = np.arange(R + 1, dtype=np.int64) * T, np.ascontiguousarray(tcols.ravel())
+            call = lambda: ctx.rank_of(indptr, indices, 0, R, exclude=ex)   # noqa: E731
+            rank, above, tied, scores, eligible = call()
+            ctx.predict_rows(0, R, out=out64)
+            t = {"targets_per_row": T, "exclude": ex is not None, "output_bytes": 8 * (4 * R * T + R)}
+            for route in (host_by_compares, host_by_sort) if T <= 10 else (host_by_sort,):
+                want = route(out64, tcols, ex)
+                assert all(np.array_equal(a.reshape(R, T) if a.size == R * T else a, w)
+                           for a, w in zip((rank, above, tied, eligible), want)), \
+                    f"rank_of ({T} targets per row) disagrees with {route.__name__} over predict_rows"
+            assert np.array_equal(scores.reshape(R, T), np.take_along_axis(out64, tcols, axis=1)), "rank_of: scores"
+            t["ineligible_targets"] = int((rank < 0).sum())
+            t["device_s"], t["device_all_s"] = median_s(call)
+            say(f"rank_of T={T}: device {t['device_s']:.6f} s")
+            kept = []                                           # the same call with every result kept alive: median_s drops a
+            t["device_results_kept_s"], t["device_results_kept_all_s"] = median_s(lambda: kept.append(call()))   # result inside the timed region
+            say(f"rank_of T={T}: device, results kept alive {t['device_results_kept_s']:.6f} s")
+            del kept
+            t["top_n_10_same_exclude_s"], t["top_n_10_same_exclude_all_s"] = median_s(lambda: ctx.top_n(10, 0, R, exclude=ex))
+            say(f"top_n(10), the same exclude: {t['top_n_10_same_exclude_s']:.6f} s")
+            if not args.device_only:
+                for route in (host_by_compares, host_by_sort) if T <= 10 else (host_by_sort,):
+                    name = "predict_rows_then_" + route.__name__
+                    t[name + "_s"], t[name + "_all_s"] = median_s(lambda: route(ctx.predict_rows(0, R, out=out64), tcols, ex))
+                    say(f"rank_of T={T}: {name} {t[name + '_s']:.6f} s")
+                best = min(v for key, v in t.items() if key.startswith("predict_rows_then_") and key.endswith("_s")
+                           and not key.endswith("_all_s"))
+                t["speedup_vs_best_host_route"] = best / t["device_s"]
+            f[f"T{T}"] = t
+        res["rank_of_leg"] = f
 
     # ---- (e) class histograms of Theta ------------------------------------------------------------------------------------------
     if "theta_hist" in legs:
