@@ -324,6 +324,47 @@ int nbmf_rank_rows(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int clip_theta,
                    int64_t* out_rank, int64_t* out_above, int64_t* out_tied, double* out_scores,
                    int64_t* out_eligible /* nrows */);
 
+/* Held-out entries kept on the device, and their Bernoulli log-likelihood summed there: the held-out curve of a fit
+ * without the factors leaving the device, and early stopping on it.  `count` index pairs of the internal m x n matrix with
+ * one byte of truth each (nonzero means x = 1), in any order, repeats allowed; 9 bytes per pair stay resident (rows and
+ * columns as int32).  The pairs are checked on the host before anything is kept: one outside [0, m) x [0, n) gives
+ * NBMF_ERR_ARG with the lowest offending position in the message, and the context keeps the eval set it had.  count == 0
+ * switches evaluation off and frees the arrays.  every >= 1 and patience >= 0 (else NBMF_ERR_ARG) say how nbmf_run uses
+ * the set, see below; they do not enter the sum.  NBMF_ERR_STATE while a communicator is attached, and nbmf_comm_init* on
+ * a context that holds an eval set returns NBMF_ERR_STATE as well.
+ *
+ * nbmf_eval_loglik: the sum over the pairs of t = log(x ? theta + eps : (1 - theta) + eps), the argument formed in that
+ * order, eps that of nbmf_set_hyper, the device library's log (nbmf_score_rows' term), where theta is bit for bit what
+ * nbmf_predict_at(..., clip_theta = 0) returns for the pair.  Summation order: the 32 pairs [32 b, 32 b + 32) make
+ * partial b (a fixed tree), and the partials are folded in a fixed order by one workgroup: the value depends on the
+ * factors, the pairs in the order given and eps only -- not on every / patience, on when it is computed or on which call
+ * computed it -- and the same evaluation twice gives the same bits.  No floating-point atomics.  Needs factors and an eval
+ * set, not data (NBMF_ERR_STATE otherwise; state rules of nbmf_predict_at); synchronises before it returns.
+ *
+ * nbmf_run on a context with an eval set is served by the launch-per-kernel engine (not the single-launch engine, not
+ * NBMF_USE_GRAPH) in batches that end on the multiples of `every`; behind each batch the set is evaluated and the host
+ * looks at the value at once (a progress callback's reports are delivered at those looks).  An evaluation is labelled
+ * with s, the number of MM iterations its factors have had -- the unit of n_iter: s = every, 2 every, ..., and the last
+ * label always equals n_iter: where max_iter is no multiple of `every` one more evaluation is made at the end, and where
+ * the tol rule ends the run between two multiples the evaluation behind that batch has seen exactly the final factors
+ * and is recorded under n_iter.  An evaluation IMPROVES if its sum is strictly greater than the best so far (the first
+ * always does); the factor images are then copied device-to-device into a snapshot, with the stream drained and nothing
+ * enqueued behind the evaluation.  With patience = p > 0 the run ends at the p-th consecutive evaluation on a multiple
+ * of `every` that does not improve: n_iter is that evaluation's s, losses[0 .. s) are final (the last one from the
+ * usual Theta-only sweep), the context's factors are those after s iterations.  patience = 0 records the curve and
+ * never stops; the losses, the factors and the curve are then bit for bit those of the run without an eval set.
+ * nbmf_run_batch on a context with an eval set returns NBMF_ERR_STATE.
+ *
+ * nbmf_get_eval: what the last nbmf_run recorded -- *n_evals evaluations (all of them, whatever cap is), the first
+ * min(cap, *n_evals) labels and sums in iters / logliks, the label of the best one (0 if none) and whether the patience
+ * rule ended the run.  Any pointer may be NULL.  nbmf_get_best_factors: the snapshot of the last run as
+ * nbmf_get_factors lays factors out (either pointer may be NULL); NBMF_ERR_STATE if the last run made no evaluation. */
+int nbmf_set_eval(nbmf_ctx* ctx, const int64_t* rows, const int64_t* cols, const uint8_t* x, int64_t count,
+                  int every, int patience);
+int nbmf_eval_loglik(nbmf_ctx* ctx, double* loglik);
+int nbmf_get_eval(nbmf_ctx* ctx, int cap, int* n_evals, int* iters, double* logliks, int* best_iter, int* stopped_early);
+int nbmf_get_best_factors(nbmf_ctx* ctx, double* W_kxm, double* H_kxn);
+
 /* Multi-GPU, one process (and one context) per GPU.  The internal matrix Y is split over the ranks along
  *   shard_axis 0: its ROWS    -> W[:, rows] is local, H is replicated; each iteration all-reduces the k x n
  *                 H-step products [P1 | P2 | loglik] (2*K*N+1 doubles) before the H-update;

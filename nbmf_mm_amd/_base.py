@@ -10,7 +10,7 @@ from sklearn.utils import check_array
 
 from . import _hip, _metrics
 from ._solver import (device_predict, device_rank_of, device_score, device_score_samples, device_theta_hist, device_top_n,
-                      nbmf_mm_restarts, nbmf_mm_solver, w_only_transform)
+                      eval_pairs, nbmf_mm_restarts, nbmf_mm_solver, w_only_transform)
 from ._utils import check_is_fitted
 
 # Accepted spellings of the two orientations: the exact strings of src/nbmf_mm/_base.py:127-137
@@ -106,16 +106,32 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         raise err
 
     # -- estimator API ---------------------------------------------------------------------------
-    def fit(self, X, y=None, mask=None):
-        """Fit the factorisation to X (entries in [0, 1]); ``mask`` marks observed entries."""
+    def fit(self, X, y=None, mask=None, eval_mask=None, eval_every=10, patience=0, restore_best=True):
+        """Fit the factorisation to X (entries in [0, 1]); ``mask`` marks observed entries.
+
+        ``eval_mask`` (dense bool / 0-1 or scipy-sparse, of X's shape): its nonzeros are HELD-OUT entries whose truth X
+        holds (0 or 1) -- normally entries ``mask`` leaves out.  They stay on the device as index pairs; every
+        ``eval_every`` iterations their Bernoulli log-likelihood under the current factors is summed there, without the
+        factors leaving the device.  With ``patience > 0`` the fit ends at the ``patience``-th consecutive
+        evaluation that does not improve on the best so far.  New attributes (only when an eval set was given):
+        ``eval_iters_`` (iterations the evaluated factors had had; the last one equals ``n_iter_``), ``eval_loglik_`` (mean
+        per held-out entry), ``eval_perplexity_`` (``exp(-eval_loglik_)``), ``best_iter_`` and ``stopped_early_``.  With
+        ``restore_best`` (the default) ``W_`` and ``components_`` are the factors at ``best_iter_``; ``loss_curve_``,
+        ``loss_`` and ``n_iter_`` stay the run's own -- they describe all ``n_iter_`` iterations that were made, not the
+        restored factors.  ``n_init > 1`` with an eval set runs the restarts one after the other and keeps, as without
+        one, the restart with the lowest final training loss.  Not available with ``n_gpus > 1`` / ``devices``."""
         X = self._validated(X, keep_sparse=True)       # sparse V stays sparse up to the device (the solver decides)
+        # every error of the eval arguments is raised here, before any device work (the solver makes the pairs again)
+        eval_pairs(X, eval_mask, eval_every, patience, "beta-dir", self.n_gpus, self.devices)
+        ev = None if eval_mask is None else dict(eval_mask=eval_mask, eval_every=eval_every, patience=patience,
+                                                 restore_best=bool(restore_best))
         if hasattr(X, "toarray"):
             if X.nnz and (X.data.min() < 0 or X.data.max() > 1):
                 raise ValueError("X must be binary")                  # :90-91 on the stored values (zeros are fine)
-            return self._fit_validated(X, mask, sparse=True)
-        return self._fit_validated(X, mask, sparse=False)
+            return self._fit_validated(X, mask, sparse=True, ev=ev)
+        return self._fit_validated(X, mask, sparse=False, ev=ev)
 
-    def _fit_validated(self, X, mask, sparse):
+    def _fit_validated(self, X, mask, sparse, ev=None):
         # "X must be binary" (:90-91).  For big inputs the device pack, which sees every entry anyway, raises
         # it (a host-side pass costs 0.3 s on the 4 GB of BASELINE configs[2], more than the upload itself);
         # small inputs -- and any input whose orientation is bad too, to keep the reference's order of
@@ -138,12 +154,13 @@ class NBMFMM(BaseEstimator, TransformerMixin):
             raise ValueError("n_init must be >= 1")
         multi = dict(n_gpus=self.n_gpus, devices=self.devices) if (int(self.n_gpus) != 1 or self.devices is not None) else {}
         try:
-            return self._run_fit(X, mask, orientation, n_init, multi)
+            return self._run_fit(X, mask, orientation, n_init, multi, ev)
         except ValueError as e:
             self._finite_or_binary_error(X, e)
 
-    def _run_fit(self, X, mask, orientation, n_init, multi):
-        if n_init > 1 and not self.verbose and not multi:
+    def _run_fit(self, X, mask, orientation, n_init, multi, ev=None):
+        curve = None
+        if n_init > 1 and not self.verbose and not multi and ev is None:
             # restarts share one upload and one library call; small problems run several at a time in one launch
             best, _ = nbmf_mm_restarts(
                 X, self.n_components, n_init, max_iter=self.max_iter, tol=self.tol, alpha=self.alpha, beta=self.beta,
@@ -156,13 +173,16 @@ class NBMFMM(BaseEstimator, TransformerMixin):
             seed = self.random_state
             if r > 0 and seed is not None:
                 seed = seed + r                                       # restarts: consecutive seeds
+            this_curve = {}                                           # the held-out curve comes back beside the 5-tuple
             result = nbmf_mm_solver(
                 Y=X, n_components=self.n_components, max_iter=self.max_iter, tol=self.tol,
                 alpha=self.alpha, beta=self.beta, W_init=self.W_init, H_init=self.H_init, mask=mask,
                 random_state=seed, verbose=self.verbose, orientation=orientation,
-                projection=self._projection(), device=self.device, **multi)
+                projection=self._projection(), device=self.device, **multi,
+                **({} if ev is None else dict(ev, _eval_out=this_curve)))
             if best is None or result[2][-1] < best[2][-1]:
                 best = result
+                curve = None if ev is None else this_curve
         W, H, losses, _, n_iter = best
         self.W_ = W
         self.components_ = H
@@ -171,6 +191,15 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         self.loss_ = losses[-1] if losses else np.inf
         self.n_iter_ = n_iter
         self.reconstruction_err_ = losses[-1] if losses else np.inf
+        for name in ("eval_iters_", "eval_loglik_", "eval_perplexity_", "best_iter_", "stopped_early_"):
+            if hasattr(self, name):
+                delattr(self, name)                                   # present only when an eval set was given
+        if curve is not None:
+            self.eval_iters_ = np.asarray(curve["iters"], dtype=np.int64)
+            self.eval_loglik_ = np.asarray(curve["logliks"], dtype=np.float64) / curve["count"]
+            self.eval_perplexity_ = np.exp(-self.eval_loglik_)
+            self.best_iter_ = int(curve["best_iter"])
+            self.stopped_early_ = bool(curve["stopped_early"])
         return self
 
     def fit_transform(self, X, y=None):

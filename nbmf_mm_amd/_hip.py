@@ -38,7 +38,7 @@ SYMBOLS = [
     "nbmf_set_exchange_panels", "nbmf_set_peer_timeout_ms", "nbmf_run_batch", "nbmf_batch_stats", "nbmf_sweep_info",
     "nbmf_upload_v", "nbmf_selftest_mfma_peak", "nbmf_engine_stats", "nbmf_source_hash", "nbmf_comm_info", "nbmf_cancel", "nbmf_variant_stats", "nbmf_device_bus_id",
     "nbmf_predict_at", "nbmf_predict_rows", "nbmf_top_n", "nbmf_score_rows", "nbmf_theta_hist",
-    "nbmf_rank_rows",
+    "nbmf_rank_rows", "nbmf_set_eval", "nbmf_eval_loglik", "nbmf_get_eval", "nbmf_get_best_factors",
 ]
 DATA_F64, DATA_U8, DATA_F32 = 0, 1, 2
 PREDICT_F64, PREDICT_U8 = 0, 1
@@ -183,6 +183,10 @@ def load():
     lib.nbmf_theta_hist.argtypes = [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]
     lib.nbmf_rank_rows.argtypes = [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p]
+    lib.nbmf_set_eval.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int]
+    lib.nbmf_eval_loglik.argtypes = [c_void_p, dp]
+    lib.nbmf_get_eval.argtypes = [c_void_p, c_int, POINTER(c_int), c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]
+    lib.nbmf_get_best_factors.argtypes = [c_void_p, c_void_p, c_void_p]
     for name in SYMBOLS:
         if name not in ("nbmf_last_error", "nbmf_source_hash"):
             getattr(lib, name).restype = c_int
@@ -522,6 +526,48 @@ class Context:
         _check(self._lib.nbmf_predict_at(self._h, rows.ctypes.data_as(c_void_p), cols.ctypes.data_as(c_void_p), int(rows.size),
                                          int(bool(clip_theta)), out.ctypes.data_as(c_void_p)))
         return out
+
+    def set_eval(self, rows, cols, x, every=10, patience=0):
+        """Keep the held-out entries ``(rows[t], cols[t])`` of the internal m x n matrix and their truth ``x[t]`` (nonzero
+        means 1) on the device (``nbmf_set_eval``): :meth:`eval_loglik` sums their log-likelihood there, and :meth:`run`
+        evaluates them every ``every`` iterations, keeps the best factors and, with ``patience > 0``, ends at the
+        ``patience``-th consecutive evaluation that does not improve (:meth:`eval_curve`, :meth:`best_factors`).  An empty
+        set switches evaluation off.  A pair outside the matrix raises ``ValueError`` naming the lowest offending
+        position, and the eval set in place stays."""
+        rows, cols = index_pairs(rows, cols)
+        x = np.asarray(x)
+        if x.shape != rows.shape:
+            raise ValueError(f"x must be as long as rows and cols (got {x.size} and {rows.size})")
+        x = np.ascontiguousarray(x != 0).view(np.uint8)
+        ptr = lambda a: a.ctypes.data_as(c_void_p)   # noqa: E731
+        _check(self._lib.nbmf_set_eval(self._h, ptr(rows), ptr(cols), ptr(x), int(rows.size), int(every), int(patience)))
+
+    def eval_loglik(self):
+        """The Bernoulli log-likelihood sum of the eval set under the factors the context holds now
+        (``nbmf_eval_loglik``): Theta at each pair is bit for bit :meth:`predict_at` with ``clip_theta=False``."""
+        v = c_double(0)
+        _check(self._lib.nbmf_eval_loglik(self._h, byref(v)))
+        return v.value
+
+    def eval_curve(self):
+        """What the last :meth:`run` recorded (``nbmf_get_eval``): ``(iters, logliks, best_iter, stopped_early)`` -- the
+        labels (iterations the evaluated factors had had; the last one equals ``n_iter``) as an int array, the sums as a
+        float64 array, the label of the best evaluation and whether the patience rule ended the run."""
+        n, best, early = c_int(0), c_int(0), c_int(0)
+        _check(self._lib.nbmf_get_eval(self._h, 0, byref(n), None, None, None, None))
+        iters = np.zeros(n.value, dtype=np.intc)
+        logliks = np.zeros(n.value, dtype=np.float64)
+        _check(self._lib.nbmf_get_eval(self._h, n.value, byref(n), iters.ctypes.data_as(c_void_p),
+                                       logliks.ctypes.data_as(c_void_p), byref(best), byref(early)))
+        return iters.astype(np.int64), logliks, best.value, bool(early.value)
+
+    def best_factors(self):
+        """The factors at the best evaluation of the last :meth:`run`, laid out as :meth:`get_factors` does
+        (``nbmf_get_best_factors``)."""
+        W = np.empty((self.k, self.m), dtype=np.float64)
+        H = np.empty((self.k, self.n), dtype=np.float64)
+        _check(self._lib.nbmf_get_best_factors(self._h, W.ctypes.data_as(c_void_p), H.ctypes.data_as(c_void_p)))
+        return W, H
 
     def _rows(self, row0, nrows):
         """``(row0, nrows)`` of a row-slab call as ints, ``nrows`` defaulting to the rest of the matrix: inside ``[0, m)``,

@@ -69,16 +69,67 @@ def upload_any(ctx, X, mask=None, transposed=False):
     return ctx.upload(_dense(X), mask=mask, transposed=transposed)
 
 
+def eval_pairs(Y, eval_mask, eval_every=10, patience=0, orientation="beta-dir", n_gpus=1, devices=None):
+    """The held-out entries of a fit as ``Context.set_eval`` takes them, after every check of the eval arguments -- none
+    needs a device: ``(rows, cols, x)`` in the internal layout (``orientation="dir-beta"`` swaps rows and columns), in
+    row-major order of that layout, ``x`` the truth ``Y`` holds at them as uint8; or None without an ``eval_mask``.
+    ``eval_mask`` is dense (bool or numeric) or scipy-sparse of Y's shape, its nonzeros the held-out entries.  Raises
+    ``ValueError`` for a wrong shape, an empty eval set, a Y value at an eval entry that is not 0 or 1, ``eval_every < 1``,
+    ``patience < 0``, ``patience > 0`` without an ``eval_mask``, and an eval set together with ``n_gpus > 1`` or
+    ``devices``."""
+    if eval_mask is not None:
+        E = eval_mask if hasattr(eval_mask, "toarray") else np.asarray(eval_mask)
+        if E.dtype != np.bool_ and not np.issubdtype(E.dtype, np.number):
+            raise ValueError(f"eval_mask must be a bool or numeric matrix (got dtype {E.dtype})")
+        if E.ndim != 2 or tuple(E.shape) != tuple(np.shape(Y)):
+            raise ValueError(f"eval_mask has shape {tuple(E.shape)}, X has {tuple(np.shape(Y))}")
+        if hasattr(E, "toarray"):
+            E = (E != 0).tocoo()
+            r, c = E.row.astype(np.int64), E.col.astype(np.int64)
+        else:
+            r, c = np.nonzero(E)
+        if r.size == 0:
+            raise ValueError("eval_mask marks no entry: the eval set is empty")
+        v = np.asarray(Y[r, c]).ravel()
+        if not np.all((v == 0) | (v == 1)):
+            raise ValueError("X must be 0 or 1 at the entries eval_mask marks")
+    if isinstance(eval_every, (bool, np.bool_)) or not isinstance(eval_every, (int, np.integer)) or eval_every < 1:
+        raise ValueError(f"eval_every must be an integer >= 1 (got {eval_every!r})")
+    if isinstance(patience, (bool, np.bool_)) or not isinstance(patience, (int, np.integer)) or patience < 0:
+        raise ValueError(f"patience must be an integer >= 0 (got {patience!r})")
+    if eval_mask is None:
+        if patience > 0:
+            raise ValueError("patience > 0 needs an eval_mask: early stopping watches the held-out log-likelihood")
+        return None
+    if int(n_gpus) != 1 or devices is not None:
+        raise ValueError("an eval set is evaluated on one GPU: eval_mask does not go with n_gpus > 1 or devices")
+    if orientation == "dir-beta":
+        r, c = c, r
+    order = np.lexsort((c, r))                         # row-major in the internal layout
+    return (np.ascontiguousarray(r[order], dtype=np.int64), np.ascontiguousarray(c[order], dtype=np.int64),
+            np.ascontiguousarray(v[order] != 0).view(np.uint8))
+
+
 def nbmf_mm_solver(Y, n_components, max_iter=500, tol=1e-5, alpha=1.2, beta=1.2, W_init=None,
                    H_init=None, mask=None, random_state=None, verbose=0, orientation="beta-dir",
-                   eps=1e-8, projection="normalize", device=0, n_gpus=1, devices=None, _ctx_hook=None):
+                   eps=1e-8, projection="normalize", device=0, n_gpus=1, devices=None, _ctx_hook=None,
+                   eval_mask=None, eval_every=10, patience=0, restore_best=True, _eval_out=None):
     """NBMF-MM on the GPU.  Returns ``(W (m,k), H (k,n), losses, 0.0, n_iter)``.
 
     Mirrors src/nbmf_mm/_solver.py:61-216 argument for argument; ``projection``, ``device`` and ``n_gpus`` / ``devices``
     are extensions.  ``time_elapsed`` is 0.0 as in the reference (:216).  ``n_gpus > 1``: the same fit with the rows of
     Y sharded over that many GPUs from this one process (``_dist.fit_in_process``: one host thread and context per GPU,
     one exchange of the K x N H-step products per iteration); ``devices`` names the GPUs (default 0 .. n_gpus-1).
+
+    ``eval_mask`` (extension; see :func:`eval_pairs`): its nonzeros are held-out entries whose truth ``Y`` holds; they
+    stay on the device, their log-likelihood is summed there every ``eval_every`` iterations, and with ``patience > 0``
+    the run ends at the ``patience``-th consecutive evaluation that does not improve.  With ``restore_best`` the factors
+    returned are those of the best evaluation; ``losses`` and ``n_iter`` are the run's own either way.  The return value
+    stays the reference's 5-tuple: the curve is left in the dict ``_eval_out`` (``iters``, ``logliks``, ``count``,
+    ``best_iter``, ``stopped_early``), which is how the estimator gets it.
     """
+    pairs = eval_pairs(Y if hasattr(Y, "toarray") or eval_mask is None else np.asarray(Y), eval_mask, eval_every, patience,
+                       orientation, n_gpus, devices)
     if int(n_gpus) != 1 or devices is not None:
         n = int(n_gpus) if devices is None else len(list(devices))
         if devices is not None and int(n_gpus) not in (1, n):
@@ -130,11 +181,21 @@ def nbmf_mm_solver(Y, n_components, max_iter=500, tol=1e-5, alpha=1.2, beta=1.2,
                     if it % 10 == 0:
                         print(f"Iter {it:4d}: Loss = {loss:.6f}", flush=True)
             ctx.set_progress(_report, every=10)
+        if pairs is not None:
+            ctx.set_eval(*pairs, every=int(eval_every), patience=int(patience))
         losses, n_iter = ctx.run(int(max_iter), float(tol))
-        Wk, Hk = ctx.get_factors()
+        stopped_early = False
+        if pairs is not None:
+            iters, logliks, best_iter, stopped_early = ctx.eval_curve()
+            if _eval_out is not None:
+                _eval_out.update(iters=iters, logliks=logliks, count=int(pairs[0].size), best_iter=best_iter,
+                                 stopped_early=stopped_early)
+        Wk, Hk = ctx.best_factors() if pairs is not None and restore_best else ctx.get_factors()
 
     losses = [float(v) for v in losses]
-    if verbose > 0 and (n_iter < int(max_iter) or (n_iter > 1 and losses[-2] != 0 and
+    if verbose > 0 and stopped_early:
+        print(f"Stopped early at iteration {n_iter}: best held-out log-likelihood at iteration {best_iter}")
+    elif verbose > 0 and (n_iter < int(max_iter) or (n_iter > 1 and losses[-2] != 0 and
                                                    abs(losses[-2] - losses[-1]) / abs(losses[-2]) < tol)):
         print(f"Converged at iteration {n_iter - 1}")   # :172-173
 

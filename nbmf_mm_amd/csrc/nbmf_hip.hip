@@ -323,6 +323,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 #include "nbmf_score_kernels.inc"
 #include "nbmf_hist_kernels.inc"
 #include "nbmf_rank_kernels.inc"
+#include "nbmf_eval_kernels.inc"
 
 }  // namespace
 
@@ -431,6 +432,23 @@ struct nbmf_ctx {
   nbmf_progress_fn progress = nullptr;
   void* progress_user = nullptr;
   int progress_every = 0;
+  // held-out evaluation (nbmf_set_eval; nbmf_eval_kernels.inc): the resident pairs, the scratch of one
+  // evaluation, the snapshot of the best factors, and what the last nbmf_run recorded
+  struct EvalWs {
+    int64_t count = 0;   // 0 = no eval set
+    int every = 0, patience = 0;
+    int *rows = nullptr, *cols = nullptr;
+    unsigned char* x = nullptr;
+    double *Wk = nullptr, *Hk = nullptr;   // k-major copies of the factors (k_major_kernel), remade per evaluation
+    double* partials = nullptr;            // one per workgroup of eval_pairs_kernel
+    double* eval_ll_d = nullptr;           // the sums: slot 0 for nbmf_eval_loglik, slot 1 + e for a run's e-th evaluation
+    int ll_cap = 0;
+    double *bestW = nullptr, *bestH = nullptr;   // the factor images Wn / Hn at the best evaluation of the last run
+    bool have_best = false;
+    std::vector<int> iters;
+    std::vector<double> logliks;
+    int best_iter = 0, stopped_early = 0;
+  } eval;
   std::atomic<int> cancelled{0};   // nbmf_cancel (any thread): sticky; runs return NBMF_ERR_STATE at the next iteration boundary
   // timing
   bool timing = false;
@@ -2329,6 +2347,52 @@ int ensure_losses(nbmf_ctx* c, int cap) {
   return NBMF_OK;
 }
 
+// ---- held-out evaluation (nbmf_eval_kernels.inc) --------------------------------------------------------
+// Room for `cap` sums at eval_ll_d (values of earlier evaluations are not kept across a growth: each is read back by the
+// host right behind its launch).
+int ensure_eval_slots(nbmf_ctx* c, int cap) {
+  auto& ev = c->eval;
+  if (cap <= ev.ll_cap) return NBMF_OK;
+  if (ev.eval_ll_d) HIPCHK(dfree(ev.eval_ll_d));
+  ev.eval_ll_d = nullptr;
+  ev.ll_cap = 0;
+  HIPCHK(dmalloc(&ev.eval_ll_d, sizeof(double) * (size_t)cap));
+  ev.ll_cap = cap;
+  return NBMF_OK;
+}
+
+// One evaluation of the context's eval set for the factors the stream holds at this point, its sum left at
+// eval_ll_d[slot]: the k-major copies of both factors, one partial per 32 pairs, the fold.  Nothing is read back here.
+int enqueue_eval(nbmf_ctx* c, int slot) {
+  auto& ev = c->eval;
+  for (const bool h : {false, true}) {
+    const long long len = h ? c->n : c->m, lenA = h ? c->nA : c->mA;
+    hipLaunchKernelGGL(k_major_kernel, dim3((unsigned)((len + PT_TILE - 1) / PT_TILE), (unsigned)((c->k + PT_TILE - 1) / PT_TILE)),
+                       dim3(PT_TILE * 8), 0, c->stream, (const double*)(h ? c->Hn : c->Wn), h ? ev.Hk : ev.Wk, c->k, len, lenA);
+    HIPCHK(hipGetLastError());
+  }
+  const long long nparts = (ev.count + EV_PAIRS - 1) / EV_PAIRS;
+  hipLaunchKernelGGL(eval_pairs_kernel, dim3((unsigned)nparts), dim3(EV_THREADS), 0, c->stream, (const double*)ev.Wk,
+                     (const double*)ev.Hk, c->k, (const int*)ev.rows, (const int*)ev.cols, (const unsigned char*)ev.x,
+                     (long long)ev.count, c->eps, ev.partials);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(eval_fold_kernel, dim3(1), dim3(EV_FOLD), 0, c->stream, (const double*)ev.partials, nparts,
+                     ev.eval_ll_d + slot);
+  HIPCHK(hipGetLastError());
+  return NBMF_OK;
+}
+
+void eval_release(nbmf_ctx* c) {   // the caller has drained the stream
+  auto& ev = c->eval;
+  void* ptrs[] = {ev.rows, ev.cols, ev.x, ev.Wk, ev.Hk, ev.partials};
+  for (void* p : ptrs)
+    if (p) dfree(p);
+  ev.rows = ev.cols = nullptr;
+  ev.x = nullptr;
+  ev.Wk = ev.Hk = ev.partials = nullptr;
+  ev.count = 0;
+}
+
 // After an upload of binary data that is observed everywhere: see mask_pad_rows_kernel (the two-state W sweep then
 // applies whatever the shape).  Called once n_obs is known; setup_workspaces has just rebuilt the lane masks.
 int mark_pad_rows_b(nbmf_ctx* c) {
@@ -2585,7 +2649,7 @@ hipError_t launch_hist_panel(nbmf_ctx* c, const RowPanels& pl, long long p0, lon
 // ------------------------------------------------------------------------------------------
 extern "C" {
 
-int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows, nbmf_theta_hist, nbmf_rank_rows: compatible additions, which a caller detects by the symbol
+int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows, nbmf_theta_hist, nbmf_rank_rows, nbmf_set_eval, nbmf_eval_loglik, nbmf_get_eval, nbmf_get_best_factors: compatible additions, which a caller detects by the symbol
 // The sources this binary was compiled from: first 12 hex digits of the SHA-256 over nbmf_hip.hip, the *.inc files (sorted
 // by name) and include/nbmf_hip.h, put in by the Makefile (tools/src_hash.sh prints the same for the tree).  A profile or a
 // bench line that quotes it can be tied to a commit; a library built by hand without the Makefile says "unstamped".
@@ -2690,7 +2754,8 @@ int nbmf_destroy(nbmf_ctx* c) {
   void* ptrs[] = {c->dataA, c->dataB, c->maskA, c->maskB, c->rowcnt, c->Wn, c->WT, c->WG, c->Hn, c->HT, c->HG,
                   c->slabH, c->slabW, c->Pbuf, c->lossbuf, c->lossfin, c->prior, c->scal, c->flags, c->losses_d, c->stage, c->stats,
                   c->sbuf, c->Qbuf, c->cstartH, c->cstartW, c->theta, c->small.slab, c->small_batch.slab, c->small_batch.table,
-                  c->small_batch.io, c->bitsA, c->bitsB};
+                  c->small_batch.io, c->bitsA, c->bitsB, c->eval.rows, c->eval.cols, c->eval.x, c->eval.Wk, c->eval.Hk,
+                  c->eval.partials, c->eval.eval_ll_d, c->eval.bestW, c->eval.bestH};
   for (void* p : ptrs)
     if (p) dfree(p);
   for (hipEvent_t e : c->ev) hipEventDestroy(e);
@@ -3088,7 +3153,18 @@ int nbmf_run(nbmf_ctx* c, int max_iter, double tol, double* losses, int* n_iter)
   if (int rc = ensure_losses(c, max_iter)) return rc;
   HIPCHK(hipMemsetAsync(c->flags, 0, sizeof(int) * 8, c->stream));
   HIPCHK(hipMemsetAsync(c->scal, 0, sizeof(double) * 8, c->stream));
-  {
+  // An eval set (nbmf_set_eval) is evaluated between iterations by launches of its own: such a run is served by the
+  // launch engine below, in batches of `every` iterations, and never replayed from a graph.
+  auto& ev = c->eval;
+  const bool evaling = ev.count > 0;
+  ev.iters.clear();
+  ev.logliks.clear();
+  ev.best_iter = 0;
+  ev.stopped_early = 0;
+  ev.have_best = false;
+  if (evaling)
+    if (int rc = ensure_eval_slots(c, 3 + max_iter / ev.every)) return rc;
+  if (!evaling) {
     bool handled = false;   // small problems: the whole run in one persistent launch
     if (int rc = run_small(c, max_iter, tol, losses, n_iter, &handled)) return rc;
     if (handled) return NBMF_OK;
@@ -3116,7 +3192,10 @@ int nbmf_run(nbmf_ctx* c, int max_iter, double tol, double* losses, int* n_iter)
   // (config 1, 100x500 K=6: 14.7k it/s replayed vs 16.5k it/s eager) -- tiny problems are bound by the
   // latency of the five dependent kernels, not by the host's launch rate -- so it is opt-in
   // (NBMF_USE_GRAPH=1), never used with a communicator or event timing.
-  const bool use_graph = env_set("NBMF_USE_GRAPH") && !is_sharded(c) && !c->timing && !progress && max_iter >= 8;
+  const bool use_graph = env_set("NBMF_USE_GRAPH") && !is_sharded(c) && !c->timing && !progress && max_iter >= 8 && !evaling;
+  int limit = max_iter;     // the iterations this run makes at most: max_iter, or the evaluation the patience rule ended it at
+  int since_best = 0;       // consecutive evaluations on a multiple of `every` that did not improve
+  double ev_val = 0.0, ev_best = 0.0;
   bool fused_fin = fin_fusable(c) && !use_graph;
   int recoveries = 0;
   int fl[8];
@@ -3168,9 +3247,10 @@ int nbmf_run(nbmf_ctx* c, int max_iter, double tol, double* losses, int* n_iter)
     }
   } guard{graph, gexec};
   for (;;) {
-    if (it < max_iter && !host_done) {
-      // the next batch of iterations; behind it (stop rule, progress reports) a look at the flags
-      const int end = std::min(max_iter, it + batch);
+    if (it < limit && !host_done) {
+      // the next batch of iterations; behind it (stop rule, progress reports) a look at the flags.  With an eval set a
+      // batch ends on the next multiple of `every` (also after a rewind has left `it` between two)
+      const int end = evaling ? (int)std::min<long long>(limit, ((long long)it / ev.every + 1) * ev.every) : std::min(max_iter, it + batch);
       for (; it < end; ++it) {
         if (c->cancelled.load(std::memory_order_relaxed)) return fail(NBMF_ERR_STATE, "cancelled (nbmf_cancel)");
         c->timing_it = it;
@@ -3192,7 +3272,43 @@ int nbmf_run(nbmf_ctx* c, int max_iter, double tol, double* losses, int* n_iter)
         if (int rc = enqueue_h_update(c)) return rc;
         if (int rc = enqueue_w_step(c, c->projection)) return rc;
       }
-      if ((tol > 0.0 || progress) && it < max_iter) {
+      if (evaling) {
+        // The factors have had `it` iterations -- or, where the tol rule has ended the run inside this batch, n_iter of
+        // them: every later kernel has returned at once -- and the evaluation enqueued here sees exactly those.  The host
+        // looks at it at once: recorded under its label (a label already recorded is the same factors again: dropped),
+        // the snapshot taken if it improves, the patience rule applied.  A batch that settle() rewinds is made again,
+        // and its evaluation with it.
+        const int slot = 1 + (int)ev.iters.size();
+        if (int rc = enqueue_eval(c, slot)) return rc;
+        HIPCHK(hipMemcpyAsync(&ev_val, ev.eval_ll_d + slot, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        bool resume = false;
+        if (int rc = settle(/*at_end=*/false, &resume)) return rc;
+        if (!resume) {
+          host_done = fl[0];
+          if (int rc = report(fl[1])) return rc;
+          const int label = host_done ? fl[1] : it;
+          if (label >= 1 && (ev.iters.empty() || label != ev.iters.back())) {
+            const bool improves = ev.iters.empty() || ev_val > ev_best;
+            ev.iters.push_back(label);
+            ev.logliks.push_back(ev_val);
+            if (improves) {   // (the stream is drained and nothing is enqueued behind the evaluation: what it saw)
+              HIPCHK(hipMemcpyAsync(ev.bestW, c->Wn, sizeof(double) * (size_t)c->KP * c->mA, hipMemcpyDeviceToDevice, c->stream));
+              HIPCHK(hipMemcpyAsync(ev.bestH, c->Hn, sizeof(double) * (size_t)c->KP * c->nA, hipMemcpyDeviceToDevice, c->stream));
+              HIPCHK(hipStreamSynchronize(c->stream));
+              ev_best = ev_val;
+              ev.best_iter = label;
+              ev.have_best = true;
+              since_best = 0;
+            } else if (label % ev.every == 0) {
+              ++since_best;
+            }
+            if (ev.patience > 0 && since_best >= ev.patience && !host_done) {
+              limit = it;   // the run ends here as one with max_iter = it would: the last loss from the Theta-only sweep
+              ev.stopped_early = 1;
+            }
+          }
+        }
+      } else if ((tol > 0.0 || progress) && it < max_iter) {
         bool resume = false;
         if (int rc = settle(/*at_end=*/false, &resume)) return rc;
         if (!resume) {
@@ -3205,10 +3321,10 @@ int nbmf_run(nbmf_ctx* c, int max_iter, double tol, double* losses, int* n_iter)
     if (!host_done) {
       // loss of the last iteration (Theta-only sweep)
       if (fused_fin) {
-        if (int rc = enqueue_a_sweep(c, false, 0, 0, max_iter - 1, tol)) return rc;
+        if (int rc = enqueue_a_sweep(c, false, 0, 0, limit - 1, tol)) return rc;
       } else {
         if (int rc = enqueue_a_sweep(c, /*with_products=*/false)) return rc;
-        if (int rc = enqueue_finalize(c, use_graph ? -1 : max_iter - 1, tol)) return rc;
+        if (int rc = enqueue_finalize(c, use_graph ? -1 : limit - 1, tol)) return rc;
       }
     }
     bool resume = false;
@@ -3221,7 +3337,9 @@ int nbmf_run(nbmf_ctx* c, int max_iter, double tol, double* losses, int* n_iter)
     }
     if (c->cancelled.load(std::memory_order_relaxed)) return fail(NBMF_ERR_STATE, "cancelled (nbmf_cancel)");
     const int nit = fl[1];
-    if (nit < 1 || nit > max_iter) return fail(NBMF_ERR_STATE, "internal: device reported n_iter=%d", nit);
+    if (nit < 1 || nit > limit) return fail(NBMF_ERR_STATE, "internal: device reported n_iter=%d", nit);
+    if (evaling && (ev.iters.empty() || ev.iters.back() != nit))
+      return fail(NBMF_ERR_STATE, "internal: the last evaluation is labelled %d, n_iter=%d", ev.iters.empty() ? 0 : ev.iters.back(), nit);
     if (int rc = report(nit)) return rc;
     HIPCHK(hipMemcpy(losses, c->losses_d, sizeof(double) * (size_t)nit, hipMemcpyDeviceToHost));
     *n_iter = nit;
@@ -3237,6 +3355,7 @@ int nbmf_run_batch(nbmf_ctx* c, int n_problems, const double* alpha, const doubl
   if (max_iter < 1) return fail(NBMF_ERR_ARG, "max_iter must be >= 1");
   if (!alpha || !beta || !W0 || !H0 || !losses || !n_iter || !W_out || !H_out) return fail(NBMF_ERR_ARG, "null argument");
   if (is_sharded(c)) return fail(NBMF_ERR_STATE, "nbmf_run_batch runs on an unsharded context (nbmf_comm_detach first)");
+  if (c->eval.count > 0) return fail(NBMF_ERR_STATE, "nbmf_run_batch does not evaluate an eval set (nbmf_set_eval with count 0 first)");
   if (int rc = set_device(c)) return rc;
   {
     bool handled = false;
@@ -3366,6 +3485,106 @@ int nbmf_predict_at(nbmf_ctx* c, const int64_t* rows, const int64_t* cols, int64
       return fail(NBMF_ERR_ARG, "index pair at position %llu is outside [0, %lld) x [0, %lld)", bad, (long long)c->m,
                   (long long)c->n);
     HIPCHK(hipMemcpyAsync(out + base, out_d, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return NBMF_OK;
+}
+
+// ---- held-out pairs resident on the device, their log-likelihood sum (nbmf_eval_kernels.inc) ------------
+int nbmf_set_eval(nbmf_ctx* c, const int64_t* rows, const int64_t* cols, const uint8_t* x, int64_t count, int every, int patience) {
+  if (!c) return fail(NBMF_ERR_ARG, "null context");
+  if (count < 0) return fail(NBMF_ERR_ARG, "count must be >= 0 (got %lld)", (long long)count);
+  if (every < 1) return fail(NBMF_ERR_ARG, "every must be >= 1 (got %d)", every);
+  if (patience < 0) return fail(NBMF_ERR_ARG, "patience must be >= 0 (got %d)", patience);
+  if (is_sharded(c)) return fail(NBMF_ERR_STATE, "held-out evaluation runs on an unsharded context (nbmf_comm_detach first)");
+  if (int rc = set_device(c)) return rc;
+  auto& ev = c->eval;
+  if (count == 0) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    eval_release(c);
+    return NBMF_OK;
+  }
+  if (!rows || !cols || !x) return fail(NBMF_ERR_ARG, "null argument");
+  if (c->m > 0x7fffffffLL || c->n > 0x7fffffffLL || count > (1LL << 35))
+    return fail(NBMF_ERR_ARG, "an eval set holds at most 2^35 pairs of a matrix with fewer than 2^31 rows and columns");
+  for (int64_t t = 0; t < count; ++t)   // before anything is kept: a refused set leaves the one in place working
+    if (rows[t] < 0 || rows[t] >= c->m || cols[t] < 0 || cols[t] >= c->n)
+      return fail(NBMF_ERR_ARG, "index pair at position %lld is outside [0, %lld) x [0, %lld)", (long long)t, (long long)c->m,
+                  (long long)c->n);
+  const size_t K = (size_t)c->k, cnt = (size_t)count;
+  const size_t nparts = (cnt + EV_PAIRS - 1) / EV_PAIRS;
+  PredictStage fresh{c->stream, {}};   // given back on every early return; emptied once the context owns the blocks
+  int *rows_d = nullptr, *cols_d = nullptr;
+  unsigned char* x_d = nullptr;
+  double *Wk = nullptr, *Hk = nullptr, *partials = nullptr;
+  HIPCHK(fresh.get(&rows_d, sizeof(int) * cnt));
+  HIPCHK(fresh.get(&cols_d, sizeof(int) * cnt));
+  HIPCHK(fresh.get(&x_d, cnt));
+  HIPCHK(fresh.get(&Wk, sizeof(double) * K * (size_t)c->m));
+  HIPCHK(fresh.get(&Hk, sizeof(double) * K * (size_t)c->n));
+  HIPCHK(fresh.get(&partials, sizeof(double) * nparts));
+  if (!ev.bestW) HIPCHK(dmalloc(&ev.bestW, sizeof(double) * (size_t)c->KP * c->mA));
+  if (!ev.bestH) HIPCHK(dmalloc(&ev.bestH, sizeof(double) * (size_t)c->KP * c->nA));
+  if (int rc = ensure_eval_slots(c, 1)) return rc;
+  {
+    std::vector<int> narrow(cnt);
+    for (const bool col : {false, true}) {
+      const int64_t* src = col ? cols : rows;
+      for (size_t t = 0; t < cnt; ++t) narrow[t] = (int)src[t];
+      HIPCHK(hipMemcpyAsync(col ? cols_d : rows_d, narrow.data(), sizeof(int) * cnt, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    HIPCHK(hipMemcpyAsync(x_d, x, cnt, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  eval_release(c);   // (the stream has just been drained)
+  fresh.blocks.clear();
+  ev.rows = rows_d;
+  ev.cols = cols_d;
+  ev.x = x_d;
+  ev.Wk = Wk;
+  ev.Hk = Hk;
+  ev.partials = partials;
+  ev.count = count;
+  ev.every = every;
+  ev.patience = patience;
+  return NBMF_OK;
+}
+
+int nbmf_eval_loglik(nbmf_ctx* c, double* loglik) {
+  if (int rc = predict_ready(c)) return rc;
+  if (c->eval.count == 0) return fail(NBMF_ERR_STATE, "no eval set on the device (nbmf_set_eval)");
+  if (!loglik) return fail(NBMF_ERR_ARG, "null output");
+  if (int rc = set_device(c)) return rc;
+  if (int rc = enqueue_eval(c, 0)) return rc;
+  HIPCHK(hipMemcpyAsync(loglik, c->eval.eval_ll_d, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return NBMF_OK;
+}
+
+int nbmf_get_eval(nbmf_ctx* c, int cap, int* n_evals, int* iters, double* logliks, int* best_iter, int* stopped_early) {
+  if (!c) return fail(NBMF_ERR_ARG, "null context");
+  if (cap < 0) return fail(NBMF_ERR_ARG, "cap must be >= 0 (got %d)", cap);
+  const auto& ev = c->eval;
+  const size_t have = ev.iters.size(), give = std::min(have, (size_t)cap);
+  if (n_evals) *n_evals = (int)have;
+  if (iters) std::copy(ev.iters.begin(), ev.iters.begin() + give, iters);
+  if (logliks) std::copy(ev.logliks.begin(), ev.logliks.begin() + give, logliks);
+  if (best_iter) *best_iter = ev.best_iter;
+  if (stopped_early) *stopped_early = ev.stopped_early;
+  return NBMF_OK;
+}
+
+int nbmf_get_best_factors(nbmf_ctx* c, double* W, double* H) {
+  if (!c) return fail(NBMF_ERR_ARG, "null context");
+  if (!c->eval.have_best) return fail(NBMF_ERR_STATE, "the last nbmf_run made no evaluation: no best factors");
+  if (int rc = set_device(c)) return rc;
+  for (const bool h : {false, true}) {
+    double* out = h ? H : W;
+    if (!out) continue;
+    launch_get_factor(c, h, h ? c->eval.bestH : c->eval.bestW, c->stage);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, c->stage, sizeof(double) * (size_t)c->k * (h ? c->n : c->m), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   return NBMF_OK;
@@ -3722,6 +3941,7 @@ static int comm_check_args(nbmf_ctx* c, int nranks, int rank, int shard_axis) {
   if (shard_axis != 0 && shard_axis != 1) return fail(NBMF_ERR_ARG, "shard_axis must be 0 (rows of Y) or 1 (columns of Y)");
   if (c->data_kind < 0) return fail(NBMF_ERR_STATE, "call nbmf_upload before attaching a communicator (global counts are reduced there)");
   if (is_sharded(c)) return fail(NBMF_ERR_STATE, "a communicator is already attached (nbmf_comm_detach first)");
+  if (c->eval.count > 0) return fail(NBMF_ERR_STATE, "the context holds an eval set (nbmf_set_eval with count 0 first): held-out evaluation runs unsharded");
   return NBMF_OK;
 }
 

@@ -107,10 +107,26 @@ __global__ __launch_bounds__(PT_TILE * 8) void k_major_kernel(const double* __re
   }
 }
 
-// out[t] = sum_k Wk[rows[t] * K + k] * Hk[cols[t] * K + k] for the `count` pairs of one chunk (Wk, Hk: k_major_kernel).
-// PA_LANES consecutive lanes share a pair: lane q adds the products of k = q, q + 8, q + 16, ... in ascending order
-// (consecutive lanes read consecutive doubles), then the 8 partial sums are folded by the xor butterfly 4, 2, 1 -- a fixed
-// order, so the value at (i, j) depends on (i, j) and the factors only.
+// Theta at one index pair, from the k-major copies: sum_k Wk[i * K + k] * Hk[j * K + k].  PA_LANES consecutive lanes share
+// the pair: lane q adds the products of k = q, q + 8, q + 16, ... in ascending order (consecutive lanes read consecutive
+// doubles), then the 8 partial sums are folded by the xor butterfly 4, 2, 1 -- a fixed order, so the value at (i, j)
+// depends on (i, j) and the factors only, and every lane of the pair ends with it.  A pair that is not `live` loads
+// nothing and yields 0; all 64 lanes of the wave must call.  predict_at_kernel and eval_pairs_kernel
+// (nbmf_eval_kernels.inc) both take their Theta from here: the same bits by construction.
+__device__ __forceinline__ double theta_at_pair(const double* __restrict__ Wk, const double* __restrict__ Hk, int K,
+                                                long long i, long long j, int q, bool live) {
+  double s = 0.0;
+  if (live) {
+    const double* __restrict__ w = Wk + (size_t)i * K;
+    const double* __restrict__ h = Hk + (size_t)j * K;
+    for (int k = q; k < K; k += PA_LANES) s = __builtin_fma(w[k], h[k], s);
+  }
+#pragma unroll
+  for (int off = PA_LANES / 2; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+  return s;
+}
+
+// out[t] = theta_at_pair(rows[t], cols[t]) for the `count` pairs of one chunk (Wk, Hk: k_major_kernel).
 // A pair whose row is outside [0, m) or whose column is outside [0, n) is never used for an address: its lanes load
 // nothing, its output is 0, and the lowest such position (base + t) is left in *bad_pos by an atomicMin.
 __global__ __launch_bounds__(256) void predict_at_kernel(const double* __restrict__ Wk, const double* __restrict__ Hk, int K,
@@ -129,14 +145,7 @@ __global__ __launch_bounds__(256) void predict_at_kernel(const double* __restric
       if (q == 0) atomicMin(bad_pos, (unsigned long long)(base + t));
     }
   }
-  double s = 0.0;
-  if (live) {
-    const double* __restrict__ w = Wk + (size_t)i * K;
-    const double* __restrict__ h = Hk + (size_t)j * K;
-    for (int k = q; k < K; k += PA_LANES) s = __builtin_fma(w[k], h[k], s);
-  }
-#pragma unroll
-  for (int off = PA_LANES / 2; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+  double s = theta_at_pair(Wk, Hk, K, i, j, q, live);
   if (t < count && q == 0) {
     if (clip) s = s < 0.0 ? 0.0 : (s > 1.0 ? 1.0 : s);
     out[t] = s;

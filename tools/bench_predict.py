@@ -18,14 +18,20 @@ that end in a synchronise (the library's predict calls do; NumPy's are synchrono
   (f) where held-out entries of those rows stand in top_n's order: Context.rank_of with 10 targets per row under a
       10 %-dense exclude and with 100 targets per row, against predict_rows float64 plus NumPy rank counting (compares of
       the whole slab per target slot, or one sort of every row and binary searches, whichever is faster), with top_n(10)
-      under the same exclude beside it for orientation.
+      under the same exclude beside it for orientation;
+  (g) the held-out log-likelihood during a fit (``eval_curve``): real dense data this time -- X at 25 % ones, 90 % of the
+      entries observed by the fit, the unobserved 10 % (and the 1 % of them with the largest draw) held out as index
+      pairs -- Context.eval_loglik on the training context against the route there was before it (get_factors, then
+      set_factors into a second context that holds the data under the dense held-out mask, then loglik_strict), and a
+      50-iteration fit with an evaluation every 10 iterations against the same fit without an eval set.
 
 The host legs are the comparison; the device path is never its own yardstick.  Before any time is taken the device and host
 results are compared at these sizes within tests/test_gpu_predict.py's bound, 2.1 K 2^-53 (|W| @ |H|) per entry; the
 ranking is compared exactly with the host selection over the device's own slab (the shape has no ties); the score sums are
 compared with the host's over the device's own slab within tests/test_gpu_score_samples.py's bound plus NumPy's own
 summation error; the class histograms and the ranks are compared for EQUALITY with NumPy's over the device's own slab.
-``--legs`` picks the legs to time (default: the first four; ``theta_hist`` and ``rank_of`` are asked for by name).
+``--legs`` picks the legs to time (default: the first four; ``theta_hist``, ``rank_of`` and ``eval_curve`` are asked for by
+name; ``eval_curve`` alone skips the factors-only context and its agreement checks).
 Prints progress lines and, last, ONE JSON line.  Needs an MI355X: there is no CPU fallback."""
 import argparse
 import json
@@ -45,12 +51,12 @@ ap.add_argument("--pairs", type=int, default=1 << 22)
 ap.add_argument("--rows", type=int, default=8192)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--legs", default="pairs,slabs,top_n,score_samples",
-                help="comma-separated: pairs, slabs, top_n, score_samples, theta_hist, rank_of")
+                help="comma-separated: pairs, slabs, top_n, score_samples, theta_hist, rank_of, eval_curve")
 ap.add_argument("--device-only", action="store_true",
                 help="theta_hist, rank_of: skip the timed host legs (for a kernel trace of the device legs)")
 args = ap.parse_args()
 legs = set(args.legs.split(","))
-assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist", "rank_of"}, f"unknown leg in {args.legs}"
+assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist", "rank_of", "eval_curve"}, f"unknown leg in {args.legs}"
 m, n, k, P, R = args.m, args.n, args.k, args.pairs, min(args.rows, args.m)
 
 
@@ -67,6 +73,77 @@ def median_s(fn):
 def say(*a):
     print(*a, flush=True)
 
+
+def eval_curve_leg():
+    """(g): see the module docstring.  Its own data and contexts; the agreement of the two routes is printed and held to
+    1e-9 relative (the second context's sweep uses the table logarithm and another order of the products)."""
+    ge = np.random.default_rng(2027)
+    X = ge.random((m, n), dtype=np.float32) < 0.25
+    u = ge.random((m, n), dtype=np.float32)
+    train_mask = u < 0.90
+    W0 = ge.uniform(0.1, 0.9, (k, m))
+    W0 /= W0.sum(0, keepdims=True)
+    H0 = ge.uniform(0.1, 0.9, (k, n))
+    h = {"observed_by_the_fit": float(train_mask.mean()), "fit_iterations": 50, "every": 10}
+    with _hip.Context(m, n, k) as train:
+        train.set_hyper(1.2, 1.2, 1e-8)
+        train.upload(X, mask=train_mask)
+        del train_mask
+
+        def fit():
+            train.set_factors(W0, H0)
+            return train.run(50, 0.0)
+
+        h["fit_plain_s"], h["fit_plain_all_s"] = median_s(fit)
+        say("50-iteration fit, no eval set", h["fit_plain_s"])
+        plain_losses = fit()[0]
+        for name, lo in (("1pct", 0.99), ("10pct", 0.90)):
+            ev = u >= lo
+            r, c = np.nonzero(ev)
+            x = X[r, c]
+            t = {"pairs": int(r.size), "share": float(r.size) / (m * n), "resident_bytes": 9 * int(r.size),
+                 "gathered_factor_bytes": 2 * k * 8 * int(r.size)}
+            with _hip.Context(m, n, k) as second:
+                second.set_hyper(1.2, 1.2, 1e-8)
+                second.upload(X, mask=ev)
+                del ev
+                assert second.n_obs() == r.size
+
+                def second_context_route():
+                    Wf, Hf = train.get_factors()
+                    second.set_factors(Wf, Hf)
+                    return second.loglik_strict()
+
+                t0 = time.perf_counter()
+                train.set_eval(r, c, x, every=10, patience=0)
+                t["set_eval_s"] = time.perf_counter() - t0
+                a, b = train.eval_loglik(), second_context_route()
+                t["eval_loglik"], t["second_context_loglik_strict"] = a, b
+                t["relative_difference"] = abs(a - b) / abs(b)
+                assert t["relative_difference"] <= 1e-9, f"eval_loglik {a!r} against the second context's {b!r}"
+                t["eval_loglik_s"], t["eval_loglik_all_s"] = median_s(train.eval_loglik)
+                say(f"{name}: eval_loglik {t['eval_loglik_s']:.6f} s ({t['pairs']} pairs)")
+                t["second_context_route_s"], t["second_context_route_all_s"] = median_s(second_context_route)
+                say(f"{name}: get_factors -> set_factors -> loglik_strict {t['second_context_route_s']:.6f} s")
+                t["eval_gathered_GBps"] = t["gathered_factor_bytes"] / t["eval_loglik_s"] / 1e9
+                t["speedup_vs_second_context"] = t["second_context_route_s"] / t["eval_loglik_s"]
+                t["device_wins"] = bool(t["eval_loglik_s"] < t["second_context_route_s"])
+            t["fit_with_eval_s"], t["fit_with_eval_all_s"] = median_s(fit)
+            losses = fit()[0]
+            assert np.array_equal(losses, plain_losses), "the eval set changed the losses of the fit"
+            t["evaluations_per_fit"] = int(train.eval_curve()[0].size)
+            t["fit_overhead"] = t["fit_with_eval_s"] / h["fit_plain_s"] - 1.0
+            say(f"{name}: 50-iteration fit with every = 10: {t['fit_with_eval_s']:.6f} s ({100 * t['fit_overhead']:+.2f} %)")
+            train.set_eval(r[:0], c[:0], x[:0])
+            h[name] = t
+    return h
+
+
+if legs == {"eval_curve"}:
+    res = {"tool": "bench_predict", "library": _hip.source_hash(), "shape": [m, n, k], "reps": args.reps,
+           "eval_curve_leg": eval_curve_leg()}
+    print(json.dumps(res))
+    sys.exit(0)
 
 g = np.random.default_rng(2024)
 W = g.uniform(0.1, 0.9, (m, k))
@@ -347,5 +424,8 @@ with _hip.Context(m, n, k) as ctx:
         ctx.set_factors(np.ascontiguousarray(W2.T), H2)
         e["spread"] = timed_legs("spread")
         res["theta_hist_leg"] = e
+
+if "eval_curve" in legs:
+    res["eval_curve_leg"] = eval_curve_leg()
 
 print(json.dumps(res))
