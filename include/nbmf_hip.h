@@ -39,6 +39,7 @@ extern "C" {
 #define NBMF_MASK_NONE 0
 #define NBMF_MASK_F64 1         /* float64 weights; Y*mask semantics of _solver.py:30-32 */
 #define NBMF_MASK_U8 2          /* bool / uint8, nonzero = observed */
+#define NBMF_MASK_BITS 3        /* bit-packed (the layout under NBMF_DATA_BITS), a set bit = observed */
 
 #define NBMF_PROJ_NORMALIZE 0   /* the reference path: /n then column renormalise, _solver.py:54,57 */
 #define NBMF_PROJ_DUCHI 1       /* README.md:27-35 extension: per-row observed count, Euclidean projection */
@@ -95,6 +96,18 @@ int nbmf_upload(nbmf_ctx* ctx, const double* x, int64_t ldx, int transposed,
 #define NBMF_DATA_F64 0
 #define NBMF_DATA_U8 1
 #define NBMF_DATA_F32 2   /* float32 data: converted on the device (exactly, as the reference's dtype=float64 conversion does): 4 bytes per entry over PCIe */
+/* BIT-PACKED operands (NBMF_DATA_BITS for x, NBMF_MASK_BITS for a mask; the two are independent, and either goes with any
+ * kind of the other).  A packed matrix of logical shape rows x n is rows x ceil(n / 8) bytes; every row is packed on its
+ * own as np.packbits(A != 0, axis=1) does: entry j of a row is bit 7 - j % 8 of its byte j / 8.  The 8 * ceil(n / 8) - n
+ * pad bits of a row's last byte mean nothing and may hold anything.  The leading dimension of a packed array is in BYTES
+ * and at least ceil(n / 8); no byte of a row beyond ceil(n / 8) - 1 is read.  One bit per entry crosses to the device, a
+ * kernel there expands it into the staging the uint8 rows are copied into, and everything behind that staging runs as
+ * it does for NBMF_DATA_U8 / NBMF_MASK_U8: every result is bit for bit that of the uint8 operand of the same values
+ * (tested).  Packed data are binary by construction: no NBMF_ERR_RANGE.  `transposed` and nbmf_set_storage as for uint8.
+ * NBMF_ERR_ARG for ldx (ldmask) < ceil(n / 8), n the row length of the array as passed.
+ * The rows go up in chunks of at most 256 MiB of staged rows (NBMF_UPLOAD_CHUNK_ROWS in the environment, a test hook,
+ * sets the chunk height instead: rounded up to a multiple of 128; every x_kind). */
+#define NBMF_DATA_BITS 3
 int nbmf_upload_v(nbmf_ctx* ctx, const void* x, int x_kind, int64_t ldx, int transposed,
                   const void* mask, int mask_kind, int64_t ldmask, int* out_flags);
 
@@ -247,6 +260,11 @@ int nbmf_predict_rows(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int clip_theta
 #define NBMF_TOP_N_MAX 256
 int nbmf_top_n(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int top, int clip_theta,
                const uint8_t* exclude, int64_t ldx, int64_t* out_cols, double* out_scores, int64_t ldout);
+/* The same with the exclude matrix in the given form: NBMF_DATA_U8 (nbmf_top_n) or NBMF_DATA_BITS (bit-packed as under
+ * nbmf_upload_v, ldx in bytes and >= ceil(n / 8), a set bit = skipped; unpacked on the device into the panel the bytes are
+ * copied into: the same result bit for bit).  NBMF_ERR_ARG for any other exclude_kind. */
+int nbmf_top_n_v(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int top, int clip_theta,
+                 const void* exclude, int exclude_kind, int64_t ldx, int64_t* out_cols, double* out_scores, int64_t ldout);
 
 /* The Bernoulli log-likelihood of Theta against data, per row and per column, for the rows [row0, row0 + nrows).
  * theta[i, j] is bit for bit the entry nbmf_predict_rows(..., clip_theta, NBMF_PREDICT_F64, ...) returns.  An entry is
@@ -273,6 +291,15 @@ int nbmf_score_rows(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int clip_theta, 
                     const uint8_t* mask /* NULL: all observed; nonzero = observed */, int64_t ldmask,
                     double* row_ll, int64_t* row_obs,   /* nrows each, either may be NULL */
                     double* col_ll, int64_t* col_obs);  /* n each, either may be NULL */
+/* The same with a kind for the mask as well, and bit-packed operands: x_kind may also be NBMF_DATA_BITS (the term of
+ * NBMF_DATA_U8), mask_kind is NBMF_MASK_NONE (mask is ignored), NBMF_MASK_U8 or NBMF_MASK_BITS.  Packed operands are laid
+ * out as under nbmf_upload_v, their leading dimension in bytes and >= ceil(n / 8); they are unpacked on the device into
+ * the panels the bytes are copied into, so every sum and count is bit for bit that of the uint8 operands of the same
+ * values.  NBMF_ERR_ARG also for an unknown mask_kind and for a NULL mask with mask_kind set. */
+int nbmf_score_rows_v(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int clip_theta, double eps,
+                      const void* x, int x_kind /* NBMF_DATA_U8 | NBMF_DATA_F64 | NBMF_DATA_BITS */, int64_t ldx,
+                      const void* mask, int mask_kind /* NBMF_MASK_NONE | NBMF_MASK_U8 | NBMF_MASK_BITS */, int64_t ldmask,
+                      double* row_ll, int64_t* row_obs, double* col_ll, int64_t* col_obs);
 
 /* The observed zeros and the observed ones of the rows [row0, row0 + nrows) of the data, counted by the Theta they got: the
  * two integer histograms that ROC AUC and a calibration curve are functions of.  theta[i, j] is bit for bit the entry
@@ -294,6 +321,11 @@ int nbmf_theta_hist(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int bins,
                     const uint8_t* x, int64_t ldx,
                     const uint8_t* mask /* NULL: all observed; nonzero = observed */, int64_t ldmask,
                     int64_t* hist /* [2][bins]: class 0 first */, int64_t* nan_count /* [2], may be NULL */);
+/* The same with kinds: x_kind NBMF_DATA_U8 or NBMF_DATA_BITS, mask_kind NBMF_MASK_NONE, NBMF_MASK_U8 or NBMF_MASK_BITS, packed
+ * operands as for nbmf_score_rows_v (leading dimension in bytes, >= ceil(n / 8)): the same counts. */
+int nbmf_theta_hist_v(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int bins,
+                      const void* x, int x_kind, int64_t ldx, const void* mask, int mask_kind, int64_t ldmask,
+                      int64_t* hist, int64_t* nan_count);
 
 /* Where given entries of Theta stand in the order nbmf_top_n ranks their row by: the position of held-out (row, column)
  * entries among all n columns, at any depth, with a few integers per entry leaving the device instead of the row.  The
@@ -323,6 +355,12 @@ int nbmf_rank_rows(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int clip_theta,
                    const uint8_t* exclude /* may be NULL */, int64_t ldx,
                    int64_t* out_rank, int64_t* out_above, int64_t* out_tied, double* out_scores,
                    int64_t* out_eligible /* nrows */);
+/* The same with the exclude matrix in the given form, as nbmf_top_n_v: NBMF_DATA_U8 or NBMF_DATA_BITS. */
+int nbmf_rank_rows_v(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int clip_theta,
+                     const int64_t* indptr, const int32_t* indices,
+                     const void* exclude, int exclude_kind, int64_t ldx,
+                     int64_t* out_rank, int64_t* out_above, int64_t* out_tied, double* out_scores,
+                     int64_t* out_eligible);
 
 /* Held-out entries kept on the device, and their Bernoulli log-likelihood summed there: the held-out curve of a fit
  * without the factors leaving the device, and early stopping on it.  `count` index pairs of the internal m x n matrix with
@@ -459,6 +497,12 @@ int nbmf_device_synchronize(int device);
 #define NBMF_SELFTEST_DIV_PAIR_B 4
 #define NBMF_SELFTEST_RCP_OF_FOUR 5
 int nbmf_selftest_unary(int device, int op, int n, const double* x, double* y);
+/* Test hook: the kernel that unpacks bit-packed operands, on the caller's arrays.  bits is rows x ceil(n / 8) bytes with
+ * leading dimension ldbits (layout: nbmf_upload_v), out is rows x ldout bytes: out goes up whole, the kernel writes the byte
+ * 0 or 1 to out[r * ldout + j] for r < rows, j < n, and out comes back whole -- columns n .. ldout - 1 as they were.
+ * NBMF_ERR_ARG, before any device call, for a NULL bits or out, a negative size, ldbits < ceil(n / 8) or ldout < n. */
+int nbmf_selftest_unpack_bits(int device, const uint8_t* bits, int64_t ldbits, int64_t rows, int64_t n,
+                              uint8_t* out, int64_t ldout);
 
 #define NBMF_SELFTEST_LOG_1024 6  /* ... with the 1024-entry table of the product sweeps (series to r^4/4) */
 #define NBMF_SELFTEST_LOG_PRODUCT 7  /* log of a sweep's running product: no table, no memory access */

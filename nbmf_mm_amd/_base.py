@@ -9,6 +9,7 @@ from sklearn.base import BaseEstimator, TransformerMixin
 from sklearn.utils import check_array
 
 from . import _hip, _metrics
+from ._packed import PackedBits
 from ._solver import (device_predict, device_rank_of, device_score, device_score_samples, device_theta_hist, device_top_n,
                       eval_pairs, nbmf_mm_restarts, nbmf_mm_solver, w_only_transform)
 from ._utils import check_is_fitted
@@ -74,6 +75,12 @@ class NBMFMM(BaseEstimator, TransformerMixin):
 
     @staticmethod
     def _validated(X, keep_sparse=False):
+        # A PackedBits is 2-D, binary and finite by construction, and check_array does not know the type: what is left of
+        # its checks is that there is at least one row and one feature.
+        if isinstance(X, PackedBits):
+            if X.shape[0] < 1 or X.shape[1] < 1:
+                raise ValueError(f"Found array with shape {X.shape}: at least one sample and one feature are required")
+            return X
         # _base.py:83 converts every input to float64.  A dense bool / uint8 matrix stays as it is here -- one byte per
         # entry up to the device, where the pack kernel reads the bytes (nbmf_upload_v): the same fit bit for bit, without
         # the 8-byte-per-entry host copy (BASELINE configs[4]: 6.1 GB instead of 49 GB).  Shape and dimension checks are
@@ -121,10 +128,17 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         restored factors.  ``n_init > 1`` with an eval set runs the restarts one after the other and keeps, as without
         one, the restart with the lowest final training loss.  Not available with ``n_gpus > 1`` / ``devices``."""
         X = self._validated(X, keep_sparse=True)       # sparse V stays sparse up to the device (the solver decides)
+        packed = isinstance(X, PackedBits)
+        if isinstance(mask, PackedBits) and mask.shape != tuple(X.shape):
+            raise ValueError(f"mask has shape {mask.shape}, X has {tuple(X.shape)}")
+        if (packed or isinstance(mask, PackedBits)) and (int(self.n_gpus) != 1 or self.devices is not None):
+            raise ValueError("PackedBits input is fitted on one GPU: it does not go with n_gpus > 1 or devices")
         # every error of the eval arguments is raised here, before any device work (the solver makes the pairs again)
         eval_pairs(X, eval_mask, eval_every, patience, "beta-dir", self.n_gpus, self.devices)
         ev = None if eval_mask is None else dict(eval_mask=eval_mask, eval_every=eval_every, patience=patience,
                                                  restore_best=bool(restore_best))
+        if packed:                                      # (bits are binary: nothing to check; `sparse` skips the dense checks)
+            return self._fit_validated(X, mask, sparse=True, ev=ev)
         if hasattr(X, "toarray"):
             if X.nnz and (X.data.min() < 0 or X.data.max() > 1):
                 raise ValueError("X must be binary")                  # :90-91 on the stored values (zeros are fine)
@@ -212,10 +226,19 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         draw of the global NumPy RNG (_base.py:162-199)."""
         check_is_fitted(self, ["components_"])
         X = self._validated(X, keep_sparse=True)
+        self._packed_features(X, mask)
         try:
             return w_only_transform(X, self.components_, mask=mask, n_iter=50, device=self.device)
         except ValueError as e:
             self._finite_or_binary_error(X, e)
+
+    def _packed_features(self, X, mask):
+        """The shape checks of packed input to :meth:`transform` / :meth:`score`, without a device: a packed X has the
+        model's features, a packed mask X's shape."""
+        if isinstance(X, PackedBits) and X.shape[1] != np.shape(self.components_)[1]:
+            raise ValueError(f"X has {X.shape[1]} features, the model has {np.shape(self.components_)[1]}")
+        if isinstance(mask, PackedBits) and mask.shape != tuple(X.shape):
+            raise ValueError(f"mask has shape {mask.shape}, X has {tuple(X.shape)}")
 
     def inverse_transform(self, W):
         """clip(W @ components_, 0, 1) (_base.py:201-210), on the host; :meth:`predict_proba` is the same on the device,
@@ -278,6 +301,14 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         a bool or numeric dtype and of shape ``(W.shape[0], n_features)``.  None passes through."""
         if a is None:
             return None
+        want = (W.shape[0], H.shape[1])
+        if isinstance(a, PackedBits):
+            if name == "targets":
+                raise ValueError("targets as PackedBits is not supported: pass them dense or scipy-sparse "
+                                 "(exclude may be packed)")
+            if a.shape != want:
+                raise ValueError(f"{name} has shape {a.shape}, the request describes {want}")
+            return a
         if not hasattr(a, "toarray"):
             a = np.asarray(a)
         if a.dtype != np.bool_ and not np.issubdtype(a.dtype, np.number):
@@ -341,6 +372,8 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         check_is_fitted(self, ["components_", "W_"])
         if mask is None:
             raise ValueError("impute needs the mask that marks the observed entries")
+        if isinstance(X, PackedBits) or isinstance(mask, PackedBits):
+            raise ValueError("impute does not take PackedBits input: its result is a dense float64 matrix (pass toarray())")
         X = self._validated(X)
         want = (np.shape(self.W_)[0], np.shape(self.components_)[1])
         if X.shape != want:
@@ -361,6 +394,7 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         As in the reference the inner ``transform`` is called WITHOUT the mask (:235)."""
         check_is_fitted(self, ["components_"])
         X = self._validated(X, keep_sparse=True)
+        self._packed_features(X, mask)
         H = np.asarray(self.components_, dtype=np.float64)
         try:
             return device_score(X, H, mask=mask, n_iter=50, device=self.device)
@@ -381,14 +415,19 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         if tuple(X.shape) != want:
             raise ValueError(f"X has shape {tuple(X.shape)}, the request describes {want}")
         inside = (lambda v: (v == 0) | (v == 1)) if exact else (lambda v: (v >= 0) & (v <= 1))
-        if hasattr(X, "toarray"):
+        if isinstance(X, PackedBits):
+            pass                                                      # (binary by construction)
+        elif hasattr(X, "toarray"):
             if X.nnz and not np.all(inside(X.data)):
                 raise ValueError("X must be binary")                  # fit's check of the stored values
         elif X.dtype != np.bool_ and not np.all(inside(X)):
             if X.dtype != np.uint8:
                 check_array(X, dtype=None)                            # NaN / inf: sklearn's own error first, as in fit
             raise ValueError("X must be binary")
-        if mask is not None:
+        if isinstance(mask, PackedBits):
+            if mask.shape != want:
+                raise ValueError(f"mask has shape {mask.shape}, the request describes {want}")
+        elif mask is not None:
             if not hasattr(mask, "toarray"):
                 mask = np.asarray(mask)
             if mask.dtype != np.bool_ and not np.issubdtype(mask.dtype, np.number):

@@ -16,6 +16,14 @@ from __future__ import annotations
 import numpy as np
 
 from . import _hip
+from ._packed import PackedBits
+
+
+def _no_packed(*operands):
+    """The sharded fits split dense or sparse arrays by rows or columns: a PackedBits is out of their scope."""
+    if any(isinstance(a, PackedBits) for a in operands):
+        raise ValueError("PackedBits input is not supported by the sharded fits (nbmf_mm_amd._dist): fit on one GPU, "
+                         "or pass toarray()")
 
 # a transport that cannot serve this job says so with NBMFHipError or -- for capability limits such as "at most
 # 16 ranks" or "too few columns to slice" (NBMF_ERR_ARG) -- ValueError; either way the ranks must still vote
@@ -248,6 +256,7 @@ def fit_row_sharded(Y_local, M_global, r0, n_components, group, max_iter=500, to
     """beta-dir fit of the global (M_global x N) matrix whose rows [r0, r0+len(Y_local)) this rank
     holds.  Every rank must call this.  Returns (W_local (m_local,k), H (k,N), losses, n_iter)."""
     from ._solver import _projection_code, upload_any
+    _no_packed(Y_local, mask_local)
     if not hasattr(Y_local, "toarray"):
         Y_local = np.asarray(Y_local, dtype=np.float64)
     m_loc, N = Y_local.shape
@@ -280,6 +289,7 @@ def fit_sharded(V_local, global_shape, offset, n_components, group, orientation=
     prints inside its loop, :165-166); the losses are the same on every rank, so one rank's callback is enough.
     """
     from ._solver import _dense, _projection_code, upload_any
+    _no_packed(V_local, mask_local)
     if not hasattr(V_local, "toarray"):
         V_local = _dense(V_local)
     M, N = global_shape
@@ -337,6 +347,7 @@ def fit_in_process(V, n_components, n_gpus, devices=None, orientation="beta-dir"
     from . import _rendezvous
     from ._solver import _draw_init, _projection_code, _touch_up
     _projection_code(projection)
+    _no_packed(V, mask)
     n_gpus = int(n_gpus)
     if n_gpus < 1:
         raise ValueError("n_gpus must be >= 1")

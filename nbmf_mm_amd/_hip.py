@@ -11,6 +11,8 @@ from ctypes import POINTER, byref, c_char_p, c_double, c_int, c_int64, c_void_p
 
 import numpy as np
 
+from ._packed import PackedBits
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 NBMF_OK = 0
@@ -20,7 +22,7 @@ NBMF_ERR_RANGE = -3
 NBMF_ERR_STATE = -4
 NBMF_ERR_COMM = -5
 
-MASK_NONE, MASK_F64, MASK_U8 = 0, 1, 2
+MASK_NONE, MASK_F64, MASK_U8, MASK_BITS = 0, 1, 2, 3
 PROJ_NORMALIZE, PROJ_DUCHI = 0, 1
 FLAG_BINARY_PATH = 1
 STORAGE = {"auto": 0, "f64": 1, "f64w": 2}
@@ -39,8 +41,9 @@ SYMBOLS = [
     "nbmf_upload_v", "nbmf_selftest_mfma_peak", "nbmf_engine_stats", "nbmf_source_hash", "nbmf_comm_info", "nbmf_cancel", "nbmf_variant_stats", "nbmf_device_bus_id",
     "nbmf_predict_at", "nbmf_predict_rows", "nbmf_top_n", "nbmf_score_rows", "nbmf_theta_hist",
     "nbmf_rank_rows", "nbmf_set_eval", "nbmf_eval_loglik", "nbmf_get_eval", "nbmf_get_best_factors",
+    "nbmf_top_n_v", "nbmf_score_rows_v", "nbmf_theta_hist_v", "nbmf_rank_rows_v", "nbmf_selftest_unpack_bits",
 ]
-DATA_F64, DATA_U8, DATA_F32 = 0, 1, 2
+DATA_F64, DATA_U8, DATA_F32, DATA_BITS = 0, 1, 2, 3
 PREDICT_F64, PREDICT_U8 = 0, 1
 TOP_N_MAX = 256
 HIST_MAX_BINS = 1024
@@ -183,6 +186,14 @@ def load():
     lib.nbmf_theta_hist.argtypes = [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]
     lib.nbmf_rank_rows.argtypes = [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p]
+    lib.nbmf_top_n_v.argtypes = [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64]
+    lib.nbmf_score_rows_v.argtypes = [c_void_p, c_int64, c_int64, c_int, c_double, c_void_p, c_int, c_int64, c_void_p, c_int,
+                                      c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.nbmf_theta_hist_v.argtypes = [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int64, c_void_p, c_int, c_int64,
+                                      c_void_p, c_void_p]
+    lib.nbmf_rank_rows_v.argtypes = [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.nbmf_selftest_unpack_bits.argtypes = [c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64]
     lib.nbmf_set_eval.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int]
     lib.nbmf_eval_loglik.argtypes = [c_void_p, dp]
     lib.nbmf_get_eval.argtypes = [c_void_p, c_int, POINTER(c_int), c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]
@@ -322,14 +333,21 @@ BYTE_KINDS = (np.bool_, np.uint8)
 ANY_KINDS = BYTE_KINDS + (np.float64,)
 
 
-def row_array(a, nrows, n, name, kinds):
+def row_array(a, nrows, n, name, kinds, packed=False):
     """A caller's ``(nrows, n)`` array as the row-slab calls of the library take it -- the ``out`` of ``predict_rows``,
     the ``exclude`` of ``top_n``, the data and the mask of ``score_rows`` and of ``theta_hist``: ``(array, kind, ld)``,
     ``kind`` DATA_U8 (a bool or uint8 array, returned as its uint8 view) or DATA_F64, ``ld`` the leading dimension in elements.  The dtype must be
     one of ``kinds`` (BYTE_KINDS, ANY_KINDS or ``(np.float64,)``), the shape ``(nrows, n)``, the stride along a row one
     element, the row stride at least n elements and whole elements -- a slice of a wider array is passed through as it is,
     nothing is copied.  The row stride of a single row or of an empty array is ignored: ``ld = n``.  Raises ``ValueError``
-    otherwise."""
+    otherwise.  With ``packed`` a :class:`PackedBits` of shape ``(nrows, n)`` is taken as well: ``(its bytes, DATA_BITS, the
+    row stride in bytes)``."""
+    if isinstance(a, PackedBits):
+        if not packed:
+            raise ValueError(f"{name} must be a NumPy array (got a PackedBits)")
+        if a.shape != (nrows, n):
+            raise ValueError(f"{name} must have shape ({nrows}, {n}) (got {a.shape})")
+        return a.bits, DATA_BITS, a.ld
     a = np.asarray(a)
     if a.dtype not in kinds:
         *first, last = [np.dtype(t).name for t in kinds]          # "bool, uint8 or float64"
@@ -376,22 +394,32 @@ class Context:
     def upload(self, x, mask=None, transposed=False):
         """x: the m x n internal matrix, or (transposed=True) the n x m user matrix whose transpose it is.
         A bool / uint8 array goes up as it is, one byte per entry, a float32 array as it is, four (``nbmf_upload_v``: the
-        device converts, exactly); anything else as float64."""
-        x = np.asarray(x)
-        if x.dtype == np.bool_ or x.dtype == np.uint8:
-            x, x_kind = np.ascontiguousarray(x).view(np.uint8), DATA_U8
-        elif x.dtype == np.float32:
-            x, x_kind = np.ascontiguousarray(x), DATA_F32
-        else:
-            x, x_kind = _f64c(x), DATA_F64
+        device converts, exactly); anything else as float64.  A :class:`PackedBits` x and / or mask goes up as bits, one
+        per entry, and is unpacked on the device (``NBMF_DATA_BITS`` / ``NBMF_MASK_BITS``): the image is that of the bool
+        arrays, bit for bit; a packed mask has x's shape (no broadcasting)."""
         want = (self.n, self.m) if transposed else (self.m, self.n)
-        if x.shape != want:
-            raise ValueError(f"data has shape {x.shape}, context expects {want}")
+        if isinstance(x, PackedBits):                      # bits up, unpacked on the device (leading dimension in bytes)
+            shape, x, x_kind, ldx = x.shape, x.bits, DATA_BITS, x.ld
+        else:
+            x = np.asarray(x)
+            if x.dtype == np.bool_ or x.dtype == np.uint8:
+                x, x_kind = np.ascontiguousarray(x).view(np.uint8), DATA_U8
+            elif x.dtype == np.float32:
+                x, x_kind = np.ascontiguousarray(x), DATA_F32
+            else:
+                x, x_kind = _f64c(x), DATA_F64
+            shape, ldx = x.shape, (x.shape[1] if x.ndim == 2 else 0)
+        if shape != want:
+            raise ValueError(f"data has shape {shape}, context expects {want}")
         kind, mptr, ldm = MASK_NONE, None, 0
-        if mask is not None:
+        if isinstance(mask, PackedBits):
+            if mask.shape != shape:
+                raise ValueError(f"a packed mask has the shape of the data: got {mask.shape}, data is {shape}")
+            kind, mptr, ldm = MASK_BITS, mask.bits.ctypes.data_as(c_void_p), mask.ld
+        elif mask is not None:
             mask = np.asarray(mask)
-            if mask.shape != x.shape:
-                mask = np.broadcast_to(mask, x.shape)      # Y * mask broadcasting, _solver.py:30
+            if mask.shape != shape:
+                mask = np.broadcast_to(mask, shape)        # Y * mask broadcasting, _solver.py:30
             if mask.dtype == np.bool_ or mask.dtype == np.uint8:
                 mask = np.ascontiguousarray(mask).view(np.uint8)
                 kind = MASK_U8
@@ -400,7 +428,7 @@ class Context:
                 kind = MASK_F64
             mptr, ldm = mask.ctypes.data_as(c_void_p), mask.shape[1]
         flags = c_int(0)
-        _check(self._lib.nbmf_upload_v(self._h, x.ctypes.data_as(c_void_p), x_kind, x.shape[1], int(bool(transposed)),
+        _check(self._lib.nbmf_upload_v(self._h, x.ctypes.data_as(c_void_p), x_kind, ldx, int(bool(transposed)),
                                        mptr, kind, ldm, byref(flags)))
         self.binary_path = bool(flags.value & FLAG_BINARY_PATH)
         return self.binary_path
@@ -578,6 +606,14 @@ class Context:
             raise ValueError(f"rows [{row0}, {row0} + {nrows}) are not inside [0, {self.m})")
         return row0, nrows
 
+    def _mask_rows(self, mask, nrows):
+        """The ``mask`` of a row-slab call as the library takes it: ``(pointer, mask kind, leading dimension)``; the array
+        behind the pointer is the caller's own, which outlives the call."""
+        if mask is None:
+            return None, MASK_NONE, 0
+        m, kind, ld = row_array(mask, nrows, self.n, "mask", BYTE_KINDS, packed=True)
+        return m.ctypes.data_as(c_void_p), MASK_BITS if kind == DATA_BITS else MASK_U8, ld
+
     def predict_rows(self, row0=0, nrows=None, clip_theta=True, threshold=None, out=None):
         """Theta for rows ``[row0, row0 + nrows)`` and all n columns (``nbmf_predict_rows``): a float64 ``(nrows, n)``
         array, or with a ``threshold`` the bool array ``Theta > threshold``, compared on the device (one byte per entry
@@ -601,18 +637,20 @@ class Context:
         without ``return_scores``).  Slot s of a row holds the s-th column in the order "Theta descending, ties by
         ascending column" and its Theta, bit for bit the entry :meth:`predict_rows` returns.  ``exclude``: a bool or uint8
         array of shape ``(nrows, n)``, nonzero = never return this column (unit stride along a row, any row stride of at
-        least n: a slice of a wider array is fine).  A NaN Theta is never returned.  A row with fewer than ``top`` columns
+        least n: a slice of a wider array is fine), or a :class:`PackedBits` of that shape (unpacked on the device: the same
+        result).  A NaN Theta is never returned.  A row with fewer than ``top`` columns
         left ends in column -1 / score NaN.  Only ``top`` entries per row come back from the device, not n."""
         top = top_n_count(top)
         row0, nrows = self._rows(row0, nrows)
-        xptr, ldx = None, 0
+        xptr, xkind, ldx = None, DATA_U8, 0
         if exclude is not None:
-            exclude, _, ldx = row_array(exclude, nrows, self.n, "exclude", BYTE_KINDS)
+            exclude, xkind, ldx = row_array(exclude, nrows, self.n, "exclude", BYTE_KINDS, packed=True)
             xptr = exclude.ctypes.data_as(c_void_p)
         cols = np.empty((nrows, top), dtype=np.int64)
         scores = np.empty((nrows, top), dtype=np.float64) if return_scores else None
-        _check(self._lib.nbmf_top_n(self._h, row0, nrows, top, int(bool(clip_theta)), xptr, ldx, cols.ctypes.data_as(c_void_p),
-                                    None if scores is None else scores.ctypes.data_as(c_void_p), top))
+        _check(self._lib.nbmf_top_n_v(self._h, row0, nrows, top, int(bool(clip_theta)), xptr, xkind, ldx,
+                                      cols.ctypes.data_as(c_void_p), None if scores is None else scores.ctypes.data_as(c_void_p),
+                                      top))
         return cols, scores
 
     def score_rows(self, x, mask=None, row0=0, nrows=None, clip_theta=True, eps=1e-8, rows=True, cols=False):
@@ -622,7 +660,8 @@ class Context:
         not asked for (``rows`` / ``cols``).  ``x``: shape ``(nrows, n)``, bool / uint8 (nonzero means 1; the term is
         ``log(x ? theta + eps : (1 - theta) + eps)``) or float64 in [0, 1] (``x log(theta + eps) + (1 - x) log((1 - theta)
         + eps)``).  ``mask``: bool / uint8 of the same shape, nonzero = observed; None: every entry.  Both may be slices of
-        wider arrays (unit stride along a row); nothing is copied on the host.  Theta is bit for bit what
+        wider arrays (unit stride along a row); nothing is copied on the host.  Either may be a :class:`PackedBits` of that
+        shape instead (one bit per entry up, unpacked on the device: the same sums and counts).  Theta is bit for bit what
         :meth:`predict_rows` returns.  Only ``nrows + n`` sums and counts come back from the device."""
         row0, nrows = self._rows(row0, nrows)
         if not rows and not cols:
@@ -630,18 +669,15 @@ class Context:
         eps = float(eps)
         if not eps >= 0.0:
             raise ValueError(f"eps must be >= 0 (got {eps})")
-        x, x_kind, ldx = row_array(x, nrows, self.n, "x", ANY_KINDS)
-        mptr, ldm = None, 0
-        if mask is not None:
-            mask, _, ldm = row_array(mask, nrows, self.n, "mask", BYTE_KINDS)
-            mptr = mask.ctypes.data_as(c_void_p)
+        x, x_kind, ldx = row_array(x, nrows, self.n, "x", ANY_KINDS, packed=True)
+        mptr, mkind, ldm = self._mask_rows(mask, nrows)
         row_ll = np.empty(nrows, dtype=np.float64) if rows else None
         row_obs = np.empty(nrows, dtype=np.int64) if rows else None
         col_ll = np.empty(self.n, dtype=np.float64) if cols else None
         col_obs = np.empty(self.n, dtype=np.int64) if cols else None
         ptr = lambda a: None if a is None else a.ctypes.data_as(c_void_p)   # noqa: E731
-        _check(self._lib.nbmf_score_rows(self._h, row0, nrows, int(bool(clip_theta)), eps, ptr(x), x_kind, ldx, mptr, ldm,
-                                         ptr(row_ll), ptr(row_obs), ptr(col_ll), ptr(col_obs)))
+        _check(self._lib.nbmf_score_rows_v(self._h, row0, nrows, int(bool(clip_theta)), eps, ptr(x), x_kind, ldx, mptr, mkind, ldm,
+                                           ptr(row_ll), ptr(row_obs), ptr(col_ll), ptr(col_obs)))
         return row_ll, row_obs, col_ll, col_obs
 
     def theta_hist(self, x, mask=None, row0=0, nrows=None, bins=256):
@@ -651,20 +687,17 @@ class Context:
         ``min(int(theta * bins), bins - 1) == b``: bin b is ``[b / bins, (b + 1) / bins)``, the last one holds 1 as well.
         A NaN Theta is counted in ``nan_count[c]`` instead.  ``x``: bool / uint8 of shape ``(nrows, n)``; ``mask``: the
         same, nonzero = observed, None: every entry.  Both may be slices of wider arrays (unit stride along a row); nothing
-        is copied on the host.  Theta is bit for bit what :meth:`predict_rows` returns.  The counts are exact: the same
+        is copied on the host; either may be a :class:`PackedBits` of that shape instead (the same counts).  Theta is bit for bit what :meth:`predict_rows` returns.  The counts are exact: the same
         whatever the panels and the order of the device's additions, and those of disjoint row ranges add up.  Only
         ``2 * bins + 2`` integers come back from the device."""
         row0, nrows = self._rows(row0, nrows)
         bins = hist_bins(bins)
-        x, _, ldx = row_array(x, nrows, self.n, "x", BYTE_KINDS)
-        mptr, ldm = None, 0
-        if mask is not None:
-            mask, _, ldm = row_array(mask, nrows, self.n, "mask", BYTE_KINDS)
-            mptr = mask.ctypes.data_as(c_void_p)
+        x, x_kind, ldx = row_array(x, nrows, self.n, "x", BYTE_KINDS, packed=True)
+        mptr, mkind, ldm = self._mask_rows(mask, nrows)
         hist = np.empty((2, bins), dtype=np.int64)
         nan_count = np.empty(2, dtype=np.int64)
-        _check(self._lib.nbmf_theta_hist(self._h, row0, nrows, bins, x.ctypes.data_as(c_void_p), ldx, mptr, ldm,
-                                         hist.ctypes.data_as(c_void_p), nan_count.ctypes.data_as(c_void_p)))
+        _check(self._lib.nbmf_theta_hist_v(self._h, row0, nrows, bins, x.ctypes.data_as(c_void_p), x_kind, ldx, mptr, mkind, ldm,
+                                           hist.ctypes.data_as(c_void_p), nan_count.ctypes.data_as(c_void_p)))
         return hist, nan_count
 
     def rank_of(self, indptr, indices, row0=0, nrows=None, exclude=None, clip_theta=True):
@@ -677,21 +710,21 @@ class Context:
         ``tied`` other columns an equal one, and ``rank = above +`` the tied columns left of j -- 0-based, the slot
         :meth:`top_n` would put j in, at any depth.  ``scores`` is Theta at the target, bit for bit the entry
         :meth:`predict_rows` returns.  A target that is itself excluded or NaN gets -1 / -1 / -1 and its Theta.
-        ``exclude`` as in :meth:`top_n`.  The cost of a row is ``ceil(targets / 8)`` passes over its n columns; only a few
+        ``exclude`` as in :meth:`top_n` (a :class:`PackedBits` included).  The cost of a row is ``ceil(targets / 8)`` passes over its n columns; only a few
         integers per target come back from the device."""
         row0, nrows = self._rows(row0, nrows)
         indptr, indices = csr_targets(indptr, indices, nrows, self.n)
-        xptr, ldx = None, 0
+        xptr, xkind, ldx = None, DATA_U8, 0
         if exclude is not None:
-            exclude, _, ldx = row_array(exclude, nrows, self.n, "exclude", BYTE_KINDS)
+            exclude, xkind, ldx = row_array(exclude, nrows, self.n, "exclude", BYTE_KINDS, packed=True)
             xptr = exclude.ctypes.data_as(c_void_p)
         count = int(indptr[-1])
         rank, above, tied = (np.full(count, -1, dtype=np.int64) for _ in range(3))
         scores = np.full(count, np.nan)
         eligible = np.empty(nrows, dtype=np.int64)
         ptr = lambda a: a.ctypes.data_as(c_void_p)   # noqa: E731
-        _check(self._lib.nbmf_rank_rows(self._h, row0, nrows, int(bool(clip_theta)), ptr(indptr), ptr(indices), xptr, ldx,
-                                        ptr(rank), ptr(above), ptr(tied), ptr(scores), ptr(eligible)))
+        _check(self._lib.nbmf_rank_rows_v(self._h, row0, nrows, int(bool(clip_theta)), ptr(indptr), ptr(indices), xptr, xkind, ldx,
+                                          ptr(rank), ptr(above), ptr(tied), ptr(scores), ptr(eligible)))
         return rank, above, tied, scores, eligible
 
     def comm_init(self, uid: bytes, nranks: int, rank: int, shard_axis: int = 0):
@@ -835,6 +868,20 @@ def selftest_unary(op, x, device=0):
     out = np.empty_like(d)
     _check(load().nbmf_selftest_unary(int(device), int(op), int(d.size), d.ctypes.data_as(c_void_p),
                                       out.ctypes.data_as(c_void_p)))
+    return out
+
+
+def selftest_unpack_bits(bits, n, out, device=0):
+    """Run the kernel that unpacks bit-packed operands on ``bits`` (2-D uint8, C-contiguous: ``shape[1]`` is its leading
+    dimension, at least ``ceil(n / 8)``) into ``out`` (2-D uint8, C-contiguous, as many rows, ``shape[1] >= n`` its leading
+    dimension), in place: ``out`` goes to the device whole and comes back whole (GPU tests)."""
+    for name, a in (("bits", bits), ("out", out)):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 2 and a.flags.c_contiguous):
+            raise ValueError(f"{name} must be a C-contiguous 2-D uint8 array")
+    if bits.shape[0] != out.shape[0]:
+        raise ValueError(f"bits has {bits.shape[0]} rows, out has {out.shape[0]}")
+    _check(load().nbmf_selftest_unpack_bits(int(device), bits.ctypes.data_as(c_void_p), bits.shape[1], bits.shape[0], int(n),
+                                            out.ctypes.data_as(c_void_p), out.shape[1]))
     return out
 
 

@@ -10,6 +10,7 @@ import contextlib
 import numpy as np
 
 from . import _hip
+from ._packed import PackedBits
 
 _PROJECTIONS = {"normalize": _hip.PROJ_NORMALIZE, "duchi": _hip.PROJ_DUCHI}
 
@@ -53,7 +54,14 @@ def _dense(X):
 
 def upload_any(ctx, X, mask=None, transposed=False):
     """Upload dense or scipy-sparse data: binary sparse patterns (with no mask or a sparse pattern mask) go up as
-    CSR (``nbmf_upload_csr``); everything else is densified first, as the reference does (:28-29,106-107)."""
+    CSR (``nbmf_upload_csr``); everything else is densified first, as the reference does (:28-29,106-107).  A
+    :class:`PackedBits` X or mask goes up as bits, with a dense operand of any kind beside it; it does not go with a
+    sparse one (``nbmf_upload_csr`` takes patterns only)."""
+    if isinstance(X, PackedBits) or isinstance(mask, PackedBits):
+        if any(hasattr(a, "toarray") and not isinstance(a, PackedBits) for a in (X, mask)):
+            raise ValueError("PackedBits input does not go with scipy-sparse input: the CSR upload (nbmf_upload_csr) takes "
+                             "patterns only (densify the sparse operand, or pack it)")
+        return ctx.upload(X if isinstance(X, PackedBits) else _dense(X), mask=mask, transposed=transposed)
     if hasattr(X, "toarray"):
         csr = _binary_pattern(X)
         csr_mask = None
@@ -76,13 +84,16 @@ def eval_pairs(Y, eval_mask, eval_every=10, patience=0, orientation="beta-dir", 
     ``eval_mask`` is dense (bool or numeric) or scipy-sparse of Y's shape, its nonzeros the held-out entries.  Raises
     ``ValueError`` for a wrong shape, an empty eval set, a Y value at an eval entry that is not 0 or 1, ``eval_every < 1``,
     ``patience < 0``, ``patience > 0`` without an ``eval_mask``, and an eval set together with ``n_gpus > 1`` or
-    ``devices``."""
+    ``devices``.  ``Y`` may be a :class:`PackedBits` (its truth is read with ``.at``); a packed ``eval_mask`` is not taken."""
+    if isinstance(eval_mask, PackedBits):
+        raise ValueError("eval_mask as PackedBits is not supported: pass it dense (bool) or scipy-sparse (X may be packed)")
     if eval_mask is not None:
+        y_shape = tuple(Y.shape) if isinstance(Y, PackedBits) else tuple(np.shape(Y))
         E = eval_mask if hasattr(eval_mask, "toarray") else np.asarray(eval_mask)
         if E.dtype != np.bool_ and not np.issubdtype(E.dtype, np.number):
             raise ValueError(f"eval_mask must be a bool or numeric matrix (got dtype {E.dtype})")
-        if E.ndim != 2 or tuple(E.shape) != tuple(np.shape(Y)):
-            raise ValueError(f"eval_mask has shape {tuple(E.shape)}, X has {tuple(np.shape(Y))}")
+        if E.ndim != 2 or tuple(E.shape) != y_shape:
+            raise ValueError(f"eval_mask has shape {tuple(E.shape)}, X has {y_shape}")
         if hasattr(E, "toarray"):
             E = (E != 0).tocoo()
             r, c = E.row.astype(np.int64), E.col.astype(np.int64)
@@ -90,7 +101,7 @@ def eval_pairs(Y, eval_mask, eval_every=10, patience=0, orientation="beta-dir", 
             r, c = np.nonzero(E)
         if r.size == 0:
             raise ValueError("eval_mask marks no entry: the eval set is empty")
-        v = np.asarray(Y[r, c]).ravel()
+        v = Y.at(r, c) if isinstance(Y, PackedBits) else np.asarray(Y[r, c]).ravel()
         if not np.all((v == 0) | (v == 1)):
             raise ValueError("X must be 0 or 1 at the entries eval_mask marks")
     if isinstance(eval_every, (bool, np.bool_)) or not isinstance(eval_every, (int, np.integer)) or eval_every < 1:
@@ -130,6 +141,8 @@ def nbmf_mm_solver(Y, n_components, max_iter=500, tol=1e-5, alpha=1.2, beta=1.2,
     """
     pairs = eval_pairs(Y if hasattr(Y, "toarray") or eval_mask is None else np.asarray(Y), eval_mask, eval_every, patience,
                        orientation, n_gpus, devices)
+    if (int(n_gpus) != 1 or devices is not None) and (isinstance(Y, PackedBits) or isinstance(mask, PackedBits)):
+        raise ValueError("PackedBits input is fitted on one GPU: it does not go with n_gpus > 1 or devices")
     if int(n_gpus) != 1 or devices is not None:
         n = int(n_gpus) if devices is None else len(list(devices))
         if devices is not None and int(n_gpus) not in (1, n):
@@ -349,14 +362,14 @@ def device_top_n(W, H, top, exclude=None, device=0):
     ``exclude`` already validated (``_hip.top_n_count``; shape ``(rows, features)``, dense of a bool / integer / floating
     dtype or scipy-sparse, nonzero = skip).  ``exclude`` is made dense one row block at a time, so the host never holds
     more than ``TOP_N_EXCLUDE_BLOCK_BYTES`` of it beyond what the caller passed.  Factors only: no data is uploaded."""
-    if hasattr(exclude, "toarray"):
+    if hasattr(exclude, "toarray") and not isinstance(exclude, PackedBits):
         exclude = exclude.tocsr()
     with _factors_only(W, H, device) as (ctx, m, n):
         if exclude is None:
             return ctx.top_n(top, 0, m, clip_theta=True)
         cols = np.empty((m, top), dtype=np.int64)
         scores = np.empty((m, top), dtype=np.float64)
-        block = max(1, min(m, TOP_N_EXCLUDE_BLOCK_BYTES // max(n, 1)))
+        block = max(1, min(m, TOP_N_EXCLUDE_BLOCK_BYTES // _row_bytes(exclude, n)))
         for r0 in range(0, m, block):
             nr = min(block, m - r0)
             x = _row_block(exclude, r0, nr, True)
@@ -373,7 +386,7 @@ def device_rank_of(W, H, targets_csr, exclude=None, device=0):
     slice of ``indptr`` and the whole ``indices``, and a row's result does not depend on the blocks.  Factors only: no data
     is uploaded."""
     indptr, indices = targets_csr
-    if hasattr(exclude, "toarray"):
+    if hasattr(exclude, "toarray") and not isinstance(exclude, PackedBits):
         exclude = exclude.tocsr()
     with _factors_only(W, H, device) as (ctx, m, n):
         if exclude is None:
@@ -382,7 +395,7 @@ def device_rank_of(W, H, targets_csr, exclude=None, device=0):
         rank, above, tied = (np.full(count, -1, dtype=np.int64) for _ in range(3))
         scores = np.full(count, np.nan)
         eligible = np.empty(m, dtype=np.int64)
-        block = max(1, min(m, TOP_N_EXCLUDE_BLOCK_BYTES // max(n, 1)))
+        block = max(1, min(m, TOP_N_EXCLUDE_BLOCK_BYTES // _row_bytes(exclude, n)))
         for r0 in range(0, m, block):
             nr = min(block, m - r0)
             x = _row_block(exclude, r0, nr, True)
@@ -398,12 +411,20 @@ def device_rank_of(W, H, targets_csr, exclude=None, device=0):
 SCORE_SAMPLES_BLOCK_BYTES = 64 << 20
 
 
+def _row_bytes(A, n):
+    """Bytes a row of ``n`` entries of a mask-like ``A`` takes on its way to the device: ``ceil(n / 8)`` packed, else n."""
+    return max((n + 7) // 8 if isinstance(A, PackedBits) else n, 1)
+
+
 def _row_block(A, r0, nr, is_mask):
     """Rows ``[r0, r0 + nr)`` of the data of ``Context.score_rows``, or of a mask (its ``mask``, the ``exclude`` of
     ``Context.top_n``), as the context takes them.  A bool / uint8 block is passed as it is; a mask of another dtype as
     ``!= 0``; other data as uint8 when the block is exactly {0, 1}, else as float64.  A sparse block is made dense first
-    (a mask as a bool block, whatever the stored dtype); a block that is not laid out row after row is copied."""
+    (a mask as a bool block, whatever the stored dtype); a block that is not laid out row after row is copied.  The rows
+    of a :class:`PackedBits` are passed as they are (a view)."""
     a = A[r0:r0 + nr]
+    if isinstance(a, PackedBits):
+        return a
     if hasattr(a, "toarray"):
         a = (a != 0).toarray() if is_mask else a.toarray()
     a = np.asarray(a)
@@ -422,13 +443,16 @@ def _row_block(A, r0, nr, is_mask):
 def _sliceable(X, mask):
     """``(X, mask, one_call)``: the data and the mask of :func:`device_score_samples` / :func:`device_theta_hist` in a form
     whose row blocks ``_row_block`` can take (sparse as CSR, anything else an ndarray), and whether they can go to the
-    device in one call as they are: both dense bool / uint8 (or no mask)."""
-    byte = lambda a: a is None or (not hasattr(a, "toarray") and a.dtype in (np.bool_, np.uint8))   # noqa: E731
-    if hasattr(X, "toarray"):
+    device in one call as they are: both dense bool / uint8 or :class:`PackedBits` (or no mask)."""
+    packed = lambda a: isinstance(a, PackedBits)   # noqa: E731
+    byte = lambda a: a is None or packed(a) or (not hasattr(a, "toarray") and a.dtype in (np.bool_, np.uint8))   # noqa: E731
+    if packed(X):
+        pass
+    elif hasattr(X, "toarray"):
         X = X.tocsr()
     elif not isinstance(X, np.ndarray):
         X = np.asarray(X)
-    if mask is not None:
+    if mask is not None and not packed(mask):
         mask = mask.tocsr() if hasattr(mask, "toarray") else np.asarray(mask)
     return X, mask, byte(X) and byte(mask)
 
@@ -479,7 +503,7 @@ def device_theta_hist(W, H, X, mask=None, bins=256, device=0):
         for r0 in range(0, m, max(block, 1)):
             nr = min(block, m - r0)
             x = _row_block(X, r0, nr, False)
-            if x.dtype == np.float64:
+            if not isinstance(x, PackedBits) and x.dtype == np.float64:
                 raise ValueError("X must be binary")
             mk = None if mask is None else _row_block(mask, r0, nr, True)
             h, c = ctx.theta_hist(x, mk, r0, nr, bins=bins)

@@ -324,6 +324,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 #include "nbmf_hist_kernels.inc"
 #include "nbmf_rank_kernels.inc"
 #include "nbmf_eval_kernels.inc"
+#include "nbmf_bits_kernels.inc"
 
 }  // namespace
 
@@ -2587,6 +2588,43 @@ hipError_t copy_rows(void* dst, size_t dst_pitch, const void* src, size_t src_pi
   return hipMemcpy2DAsync(dst, dst_pitch, src, src_pitch, width, rows, kind, stream);
 }
 
+// ---- bit-packed operands (NBMF_DATA_BITS / NBMF_MASK_BITS; nbmf_bits_kernels.inc) ---------------------------
+inline long long packed_ld(long long n) { return (n + 7) / 8; }   // bytes of a packed row of n entries
+
+// unpack_bits_kernel over rows x n entries, with the widest store that both the address of out_d and ldout are a multiple of.
+hipError_t launch_unpack_bits(const unsigned char* bits_d, long long ldbits, long long rows, long long n, unsigned char* out_d,
+                              long long ldout, hipStream_t stream) {
+  if (rows <= 0 || n <= 0) return hipSuccess;
+  const unsigned long long align = (unsigned long long)(uintptr_t)out_d | (unsigned long long)ldout;
+  const int out_elt = align % 8 == 0 ? 8 : align % 4 == 0 ? 4 : 1;
+  const long long spans = (n + out_elt - 1) / out_elt;
+  dim3 grid((unsigned)((spans + UB_THREADS - 1) / UB_THREADS), (unsigned)std::min<long long>(rows, 65535));
+  hipLaunchKernelGGL(unpack_bits_kernel, grid, dim3(UB_THREADS), 0, stream, bits_d, ldbits, rows, n, out_d, ldout, out_elt);
+  return hipGetLastError();
+}
+
+// `rows` rows of a caller's operand into the staging panel dst (leading dimension ldp entries of elt bytes) -- what the
+// upload and the four row-slab calls that take data do per chunk or panel.  An operand of elt bytes per entry (ld in
+// entries) is copied (copy_rows).  A packed one (ld in bytes; elt is 1) goes up as it is into bits_d, a block of at least
+// rows x packed_ld(n) bytes from the call's staging, and is unpacked into dst on the stream: the panel then holds the
+// bytes the uint8 operand of the same values would have put there.
+hipError_t stage_rows_as_bytes(unsigned char* bits_d, const void* src, bool packed, size_t elt, size_t ld, size_t n, size_t rows,
+                               void* dst, size_t ldp, hipStream_t stream) {
+  if (!packed) return copy_rows(dst, ldp * elt, src, ld * elt, n * elt, rows, hipMemcpyHostToDevice, stream);
+  const size_t nb = (size_t)packed_ld((long long)n);
+  hipError_t e = copy_rows(bits_d, nb, src, ld, nb, rows, hipMemcpyHostToDevice, stream);
+  if (e != hipSuccess) return e;
+  return launch_unpack_bits(bits_d, (long long)nb, (long long)rows, (long long)n, (unsigned char*)dst, (long long)ldp, stream);
+}
+
+// The leading-dimension rule of a row operand of a row-slab call, packed or not: NBMF_OK, or the error.
+int check_row_ld(const char* what, int64_t ld, bool packed, int64_t n) {
+  if (packed && ld < packed_ld(n))
+    return fail(NBMF_ERR_ARG, "%s %lld is less than ceil(n / 8) = %lld", what, (long long)ld, (long long)packed_ld(n));
+  if (!packed && ld < n) return fail(NBMF_ERR_ARG, "%s %lld is less than n = %lld", what, (long long)ld, (long long)n);
+  return NBMF_OK;
+}
+
 // How a row-slab call walks its rows [row0, end), in panels that share one staging and end in a stream synchronise each:
 //   for (long long p0 = row0, pn; p0 < pl.end; p0 += pn) { pn = pl.rows_at(p0); ... }
 // A panel is NBMF_PREDICT_PANEL_ROWS rows high, or else what 256 MiB of staging hold at row_bytes per panel row, rounded
@@ -2791,9 +2829,12 @@ int nbmf_upload(nbmf_ctx* c, const double* x, int64_t ldx, int transposed, const
 int nbmf_upload_v(nbmf_ctx* c, const void* xv, int x_kind, int64_t ldx, int transposed, const void* mask, int mask_kind,
                   int64_t ldmask, int* out_flags) {
   if (!c || !xv) return fail(NBMF_ERR_ARG, "null context or data");
-  if (x_kind != NBMF_DATA_F64 && x_kind != NBMF_DATA_U8 && x_kind != NBMF_DATA_F32)
-    return fail(NBMF_ERR_ARG, "x_kind must be NBMF_DATA_F64, NBMF_DATA_U8 or NBMF_DATA_F32");
-  const size_t xsz = x_kind == NBMF_DATA_U8 ? 1 : (x_kind == NBMF_DATA_F32 ? 4 : 8);   // bytes per element of the host array
+  if (x_kind != NBMF_DATA_F64 && x_kind != NBMF_DATA_U8 && x_kind != NBMF_DATA_F32 && x_kind != NBMF_DATA_BITS)
+    return fail(NBMF_ERR_ARG, "x_kind must be NBMF_DATA_F64, NBMF_DATA_U8, NBMF_DATA_F32 or NBMF_DATA_BITS");
+  if (mask && (mask_kind < NBMF_MASK_NONE || mask_kind > NBMF_MASK_BITS)) return fail(NBMF_ERR_ARG, "unknown mask_kind %d", mask_kind);
+  // A packed operand is unpacked on the device into the byte staging of the uint8 one: from there on it IS one
+  const bool xbits = x_kind == NBMF_DATA_BITS, mbits = mask && mask_kind == NBMF_MASK_BITS;
+  const size_t xsz = x_kind == NBMF_DATA_U8 || xbits ? 1 : (x_kind == NBMF_DATA_F32 ? 4 : 8);   // bytes per element of the staged rows
   const double* x = (const double*)xv;
   const unsigned char* xb = (const unsigned char*)xv;
   if (mask_kind != NBMF_MASK_NONE && !mask) return fail(NBMF_ERR_ARG, "mask_kind set but mask is NULL");
@@ -2801,7 +2842,11 @@ int nbmf_upload_v(nbmf_ctx* c, const void* xv, int x_kind, int64_t ldx, int tran
   if (is_sharded(c)) return fail(NBMF_ERR_STATE, "upload before attaching a communicator");
   if (int rc = set_device(c)) return rc;
   const int64_t U = transposed ? c->n : c->m, V = transposed ? c->m : c->n;
-  if (ldx < V || (mask && ldmask < V)) return fail(NBMF_ERR_ARG, "leading dimension smaller than the row length");
+  if (xbits && ldx < packed_ld(V))
+    return fail(NBMF_ERR_ARG, "ldx %lld is less than ceil(n / 8) = %lld", (long long)ldx, (long long)packed_ld(V));
+  if (mbits && ldmask < packed_ld(V))
+    return fail(NBMF_ERR_ARG, "ldmask %lld is less than ceil(n / 8) = %lld", (long long)ldmask, (long long)packed_ld(V));
+  if ((!xbits && ldx < V) || (mask && !mbits && ldmask < V)) return fail(NBMF_ERR_ARG, "leading dimension smaller than the row length");
 
   // cheap host-side guess of the storage path from a sample (the device pack verifies it exactly);
   // NBMF_FORCE_F64=1 keeps binary data on the 8-byte path (measurement only)
@@ -2812,7 +2857,8 @@ int nbmf_upload_v(nbmf_ctx* c, const void* xv, int x_kind, int64_t ldx, int tran
     for (int64_t u = 0; u < rows && (guess_bin || guess_mask_bin); ++u) {
       const int64_t uu = (U - 1) * u / (rows > 1 ? rows - 1 : 1);
       for (int64_t v = 0; v < V && v < 4096; ++v) {
-        const double xe = x_kind == NBMF_DATA_U8 ? (double)xb[uu * ldx + v]
+        const double xe = xbits ? 0.0   // (packed operands are binary by construction: not sampled)
+                          : x_kind == NBMF_DATA_U8 ? (double)xb[uu * ldx + v]
                           : x_kind == NBMF_DATA_F32 ? (double)((const float*)xv)[uu * ldx + v] : x[uu * ldx + v];
         if (xe != 0.0 && xe != 1.0) guess_bin = false;
         if (mask_kind == NBMF_MASK_F64) {
@@ -2838,8 +2884,11 @@ int nbmf_upload_v(nbmf_ctx* c, const void* xv, int x_kind, int64_t ldx, int tran
   up_mark("host sample");
   const size_t tiles = (size_t)(c->mA / 16) * (c->nA / 16);
   // staging chunk: <= 256 MiB of raw rows and <= 32768 tile rows (grid.y limit of the pack launch)
-  const int64_t chunk_rows_max =
-      std::min<int64_t>(32768 * 16, std::max<int64_t>(PAD, ((int64_t)(256ll << 20) / (V * (int64_t)xsz)) / PAD * PAD));
+  // (NBMF_UPLOAD_CHUNK_ROWS, a test hook, replaces the 256 MiB height: rounded up to a multiple of PAD, the grid limit stays)
+  const int64_t chunk_rows_env = env_int<int64_t>("NBMF_UPLOAD_CHUNK_ROWS", 0);
+  const int64_t chunk_rows_max = std::min<int64_t>(
+      32768 * 16, chunk_rows_env > 0 ? round_up(std::min<int64_t>(chunk_rows_env, 32768 * 16), PAD)
+                                     : std::max<int64_t>(PAD, ((int64_t)(256ll << 20) / (V * (int64_t)xsz)) / PAD * PAD));
   char* raw = nullptr;
   void* rawm = nullptr;
   struct StagingGuard {   // the raw staging buffers never outlive this call, whichever way it returns
@@ -2854,6 +2903,10 @@ int nbmf_upload_v(nbmf_ctx* c, const void* xv, int x_kind, int64_t ldx, int tran
   const int64_t chunk_rows = std::min<int64_t>(round_up(U, PAD), chunk_rows_max);
   HIPCHK(dmalloc(&raw, (size_t)chunk_rows * V * xsz));
   if (mask) HIPCHK(dmalloc(&rawm, (size_t)chunk_rows * V * msz));
+  PredictStage bit_stage{c->stream, {}};   // the packed rows of a chunk, as they came
+  unsigned char *xbits_d = nullptr, *mbits_d = nullptr;
+  if (xbits) HIPCHK(bit_stage.get(&xbits_d, (size_t)chunk_rows * packed_ld(V)));
+  if (mbits) HIPCHK(bit_stage.get(&mbits_d, (size_t)chunk_rows * packed_ld(V)));
 
   up_mark("staging buffers");
   int rc = NBMF_OK;
@@ -2887,9 +2940,16 @@ int nbmf_upload_v(nbmf_ctx* c, const void* xv, int x_kind, int64_t ldx, int tran
       const int64_t urows_pad = std::min<int64_t>(chunk_rows, round_up(U, PAD) - u0);
       const int64_t urows = std::max<int64_t>(0, std::min<int64_t>(U - u0, urows_pad));
       if (urows > 0) {
-        HIPCHK(hipMemcpy2DAsync(raw, (size_t)V * xsz, xb + (size_t)u0 * ldx * xsz, (size_t)ldx * xsz, (size_t)V * xsz, (size_t)urows,
-                                hipMemcpyHostToDevice, c->stream));
-        if (mask)
+        if (xbits)
+          HIPCHK(stage_rows_as_bytes(xbits_d, xb + (size_t)u0 * ldx, true, 1, (size_t)ldx, (size_t)V, (size_t)urows, raw, (size_t)V,
+                                     c->stream));
+        else
+          HIPCHK(hipMemcpy2DAsync(raw, (size_t)V * xsz, xb + (size_t)u0 * ldx * xsz, (size_t)ldx * xsz, (size_t)V * xsz,
+                                  (size_t)urows, hipMemcpyHostToDevice, c->stream));
+        if (mbits)
+          HIPCHK(stage_rows_as_bytes(mbits_d, (const char*)mask + (size_t)u0 * ldmask, true, 1, (size_t)ldmask, (size_t)V,
+                                     (size_t)urows, rawm, (size_t)V, c->stream));
+        else if (mask)
           HIPCHK(hipMemcpy2DAsync(rawm, (size_t)V * msz, (const char*)mask + (size_t)u0 * ldmask * msz,
                                   (size_t)ldmask * msz, (size_t)V * msz, (size_t)urows, hipMemcpyHostToDevice,
                                   c->stream));
@@ -2902,9 +2962,9 @@ int nbmf_upload_v(nbmf_ctx* c, const void* xv, int x_kind, int64_t ldx, int tran
       }
       PackArgs a{};
       a.x = raw;
-      a.x_kind = x_kind;
+      a.x_kind = xbits ? NBMF_DATA_U8 : x_kind;
       a.mask = mask ? rawm : nullptr;
-      a.mask_kind = mask_kind;
+      a.mask_kind = mbits ? NBMF_MASK_U8 : mask_kind;
       a.ldx = V;
       a.ldmask = V;
       a.u0 = u0;
@@ -3621,31 +3681,42 @@ int nbmf_predict_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, 
 // entry nbmf_predict_rows returns), then the selection, then top entries per row back to the host instead of n.
 int nbmf_top_n(nbmf_ctx* c, int64_t row0, int64_t nrows, int top, int clip_theta, const uint8_t* exclude, int64_t ldx,
                int64_t* out_cols, double* out_scores, int64_t ldout) {
+  return nbmf_top_n_v(c, row0, nrows, top, clip_theta, exclude, NBMF_DATA_U8, ldx, out_cols, out_scores, ldout);
+}
+
+int nbmf_top_n_v(nbmf_ctx* c, int64_t row0, int64_t nrows, int top, int clip_theta, const void* exclude, int exclude_kind,
+                 int64_t ldx, int64_t* out_cols, double* out_scores, int64_t ldout) {
   if (int rc = predict_ready(c)) return rc;
   if (top < 1 || top > NBMF_TOP_N_MAX) return fail(NBMF_ERR_ARG, "top must be in [1, %d] (got %d)", NBMF_TOP_N_MAX, top);
   if (int rc = check_rows(c, row0, nrows)) return rc;
   if (ldout < top) return fail(NBMF_ERR_ARG, "ldout %lld is less than top = %d", (long long)ldout, top);
-  if (exclude && ldx < c->n) return fail(NBMF_ERR_ARG, "ldx %lld is less than n = %lld", (long long)ldx, (long long)c->n);
+  if (exclude_kind != NBMF_DATA_U8 && exclude_kind != NBMF_DATA_BITS) return fail(NBMF_ERR_ARG, "unknown exclude_kind %d", exclude_kind);
+  const bool exbits = exclude_kind == NBMF_DATA_BITS;
+  if (exclude)
+    if (int rc = check_row_ld("ldx", ldx, exbits, c->n)) return rc;
   if (nrows == 0) return NBMF_OK;
   if (!out_cols) return fail(NBMF_ERR_ARG, "null output");
   if (int rc = set_device(c)) return rc;
   static_assert(NBMF_TOP_N_MAX == TN_MAX, "the kernel's entry list holds NBMF_TOP_N_MAX slots");
   const long long n = c->n;
   RowPanels pl;   // (the panel of nbmf_predict_rows, float64)
-  if (int rc = plan_row_panels(c, "nbmf_top_n", row0, nrows, (size_t)panel_ld(c) * sizeof(double), false, &pl)) return rc;
+  const size_t exb = exclude && exbits ? (size_t)packed_ld(n) : 0;   // a packed exclude row's share of the staging
+  if (int rc = plan_row_panels(c, "nbmf_top_n", row0, nrows, (size_t)panel_ld(c) * sizeof(double) + exb, false, &pl)) return rc;
   const size_t rows = (size_t)pl.stage_rows(), w64 = sizeof(int64_t) * (size_t)top, pitch = sizeof(int64_t) * (size_t)ldout;
   PredictStage st{c->stream, {}};
   double *panel_d = nullptr, *scores_d = nullptr;
   long long* cols_d = nullptr;
-  unsigned char* ex_d = nullptr;
+  unsigned char *ex_d = nullptr, *exbits_d = nullptr;
   HIPCHK(st.get(&panel_d, sizeof(double) * rows * pl.ldp));
   HIPCHK(st.get(&cols_d, rows * w64));
   if (out_scores) HIPCHK(st.get(&scores_d, rows * w64));
   if (exclude) HIPCHK(st.get(&ex_d, rows * n));
+  if (exb) HIPCHK(st.get(&exbits_d, rows * exb));
   for (long long p0 = row0, pn; p0 < pl.end; p0 += pn) {
     pn = pl.rows_at(p0);
     const size_t done = (size_t)(p0 - row0);
-    if (exclude) HIPCHK(copy_rows(ex_d, n, exclude + done * ldx, ldx, n, pn, hipMemcpyHostToDevice, c->stream));
+    if (exclude)
+      HIPCHK(stage_rows_as_bytes(exbits_d, (const char*)exclude + done * ldx, exbits, 1, ldx, n, pn, ex_d, n, c->stream));
     HIPCHK(launch_theta_panel(c, pl, p0, pn, NBMF_PREDICT_F64, clip_theta, 0.0, panel_d));
     hipLaunchKernelGGL(top_n_kernel, dim3((unsigned)pn), dim3(TN_THREADS), 0, c->stream, (const double*)panel_d, pl.ldp, n,
                        (const unsigned char*)ex_d, n, top, cols_d, scores_d);
@@ -3664,11 +3735,24 @@ int nbmf_top_n(nbmf_ctx* c, int64_t row0, int64_t nrows, int top, int clip_theta
 // straddles two of them and a column's chain of additions is the same whatever the panel height.
 int nbmf_score_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, double eps, const void* x, int x_kind, int64_t ldx,
                     const uint8_t* mask, int64_t ldmask, double* row_ll, int64_t* row_obs, double* col_ll, int64_t* col_obs) {
+  return nbmf_score_rows_v(c, row0, nrows, clip_theta, eps, x, x_kind, ldx, mask, mask ? NBMF_MASK_U8 : NBMF_MASK_NONE, ldmask, row_ll,
+                           row_obs, col_ll, col_obs);
+}
+
+int nbmf_score_rows_v(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, double eps, const void* x, int x_kind, int64_t ldx,
+                      const void* mask, int mask_kind, int64_t ldmask, double* row_ll, int64_t* row_obs, double* col_ll,
+                      int64_t* col_obs) {
   if (int rc = predict_ready(c)) return rc;
   if (int rc = check_rows(c, row0, nrows)) return rc;
-  if (x_kind != NBMF_DATA_U8 && x_kind != NBMF_DATA_F64) return fail(NBMF_ERR_ARG, "unknown x_kind %d", x_kind);
-  if (ldx < c->n) return fail(NBMF_ERR_ARG, "ldx %lld is less than n = %lld", (long long)ldx, (long long)c->n);
-  if (mask && ldmask < c->n) return fail(NBMF_ERR_ARG, "ldmask %lld is less than n = %lld", (long long)ldmask, (long long)c->n);
+  if (x_kind != NBMF_DATA_U8 && x_kind != NBMF_DATA_F64 && x_kind != NBMF_DATA_BITS) return fail(NBMF_ERR_ARG, "unknown x_kind %d", x_kind);
+  if (mask_kind != NBMF_MASK_NONE && mask_kind != NBMF_MASK_U8 && mask_kind != NBMF_MASK_BITS)
+    return fail(NBMF_ERR_ARG, "unknown mask_kind %d", mask_kind);
+  if (mask_kind != NBMF_MASK_NONE && !mask) return fail(NBMF_ERR_ARG, "mask_kind set but mask is NULL");
+  if (mask_kind == NBMF_MASK_NONE) mask = nullptr;
+  const bool xbits = x_kind == NBMF_DATA_BITS, mbits = mask_kind == NBMF_MASK_BITS;
+  if (int rc = check_row_ld("ldx", ldx, xbits, c->n)) return rc;
+  if (mask)
+    if (int rc = check_row_ld("ldmask", ldmask, mbits, c->n)) return rc;
   if (!(eps >= 0.0)) return fail(NBMF_ERR_ARG, "eps must be >= 0 (got %g)", eps);
   if (!row_ll && !row_obs && !col_ll && !col_obs) return fail(NBMF_ERR_ARG, "no output requested");
   const long long n = c->n;
@@ -3684,19 +3768,22 @@ int nbmf_score_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, do
   const long long ldp = panel_ld(c);
   const long long strips = (n + PR_STRIP - 1) / PR_STRIP;      // the strips that hold a real column
   // the budget of nbmf_predict_rows over everything a panel row stages: data, mask, its strip partials, its share of a block's
+  // (and the packed rows as they came, where an operand is packed)
   const size_t per_row = (size_t)ldp * (elt + (mask ? 1 : 0)) + (want_rows ? (size_t)strips * 12 + 16 : 0) +
-                         (want_cols ? ((size_t)ldp * 12 + 15) / 16 : 0);
+                         (want_cols ? ((size_t)ldp * 12 + 15) / 16 : 0) + (size_t)packed_ld(n) * ((xbits ? 1 : 0) + (mbits ? 1 : 0));
   RowPanels pl;
   if (int rc = plan_row_panels(c, "nbmf_score_rows", row0, nrows, per_row, true, &pl)) return rc;
   const long long stage_rows = pl.stage_rows(), max_blocks = stage_rows / 16 + 2;   // (no panel touches more 16-row blocks)
   PredictStage st{c->stream, {}};
   char* x_d = nullptr;
-  unsigned char* m_d = nullptr;
+  unsigned char *m_d = nullptr, *xbits_d = nullptr, *mbits_d = nullptr;
   double *rpart_d = nullptr, *cpart_d = nullptr, *row_ll_d = nullptr, *col_ll_d = nullptr;
   int *rcnt_d = nullptr, *ccnt_d = nullptr;
   long long *row_obs_d = nullptr, *col_obs_d = nullptr;
   HIPCHK(st.get(&x_d, (size_t)stage_rows * ldp * elt));
   if (mask) HIPCHK(st.get(&m_d, (size_t)stage_rows * ldp));
+  if (xbits) HIPCHK(st.get(&xbits_d, (size_t)stage_rows * packed_ld(n)));
+  if (mbits) HIPCHK(st.get(&mbits_d, (size_t)stage_rows * packed_ld(n)));
   if (want_rows) {
     HIPCHK(st.get(&rpart_d, sizeof(double) * (size_t)strips * stage_rows));
     HIPCHK(st.get(&rcnt_d, sizeof(int) * (size_t)strips * stage_rows));
@@ -3714,9 +3801,9 @@ int nbmf_score_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, do
   for (long long p0 = row0, pn; p0 < pl.end; p0 += pn) {
     pn = pl.rows_at(p0);   // (p0 + pn is a multiple of 16, or the end)
     const size_t done = (size_t)(p0 - row0);
-    HIPCHK(copy_rows(x_d, ldp * elt, (const char*)x + done * ldx * elt, ldx * elt, n * elt, pn, hipMemcpyHostToDevice, c->stream));
-    if (mask) HIPCHK(copy_rows(m_d, ldp, mask + done * ldmask, ldmask, n, pn, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(launch_score_panel(c, pl, p0, pn, x_kind, clip_theta, eps, x_d, m_d, rpart_d, rcnt_d, cpart_d, ccnt_d));
+    HIPCHK(stage_rows_as_bytes(xbits_d, (const char*)x + done * ldx * elt, xbits, elt, ldx, n, pn, x_d, ldp, c->stream));
+    if (mask) HIPCHK(stage_rows_as_bytes(mbits_d, (const char*)mask + done * ldmask, mbits, 1, ldmask, n, pn, m_d, ldp, c->stream));
+    HIPCHK(launch_score_panel(c, pl, p0, pn, xbits ? NBMF_DATA_U8 : x_kind, clip_theta, eps, x_d, m_d, rpart_d, rcnt_d, cpart_d, ccnt_d));
     if (want_rows) {
       hipLaunchKernelGGL(score_rows_finish_kernel, dim3((unsigned)((pn + 255) / 256)), dim3(256), 0, c->stream,
                          (const double*)rpart_d, (const int*)rcnt_d, pn, strips, row_ll_d, row_obs_d);
@@ -3746,11 +3833,23 @@ int nbmf_score_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, do
 // its rows counted in the panel that holds it).
 int nbmf_theta_hist(nbmf_ctx* c, int64_t row0, int64_t nrows, int bins, const uint8_t* x, int64_t ldx, const uint8_t* mask,
                     int64_t ldmask, int64_t* hist, int64_t* nan_count) {
+  return nbmf_theta_hist_v(c, row0, nrows, bins, x, NBMF_DATA_U8, ldx, mask, mask ? NBMF_MASK_U8 : NBMF_MASK_NONE, ldmask, hist, nan_count);
+}
+
+int nbmf_theta_hist_v(nbmf_ctx* c, int64_t row0, int64_t nrows, int bins, const void* x, int x_kind, int64_t ldx, const void* mask,
+                      int mask_kind, int64_t ldmask, int64_t* hist, int64_t* nan_count) {
   if (int rc = predict_ready(c)) return rc;
   if (int rc = check_rows(c, row0, nrows)) return rc;
   if (bins < 1 || bins > NBMF_HIST_MAX_BINS) return fail(NBMF_ERR_ARG, "bins must be in [1, %d] (got %d)", NBMF_HIST_MAX_BINS, bins);
-  if (ldx < c->n) return fail(NBMF_ERR_ARG, "ldx %lld is less than n = %lld", (long long)ldx, (long long)c->n);
-  if (mask && ldmask < c->n) return fail(NBMF_ERR_ARG, "ldmask %lld is less than n = %lld", (long long)ldmask, (long long)c->n);
+  if (x_kind != NBMF_DATA_U8 && x_kind != NBMF_DATA_BITS) return fail(NBMF_ERR_ARG, "unknown x_kind %d", x_kind);
+  if (mask_kind != NBMF_MASK_NONE && mask_kind != NBMF_MASK_U8 && mask_kind != NBMF_MASK_BITS)
+    return fail(NBMF_ERR_ARG, "unknown mask_kind %d", mask_kind);
+  if (mask_kind != NBMF_MASK_NONE && !mask) return fail(NBMF_ERR_ARG, "mask_kind set but mask is NULL");
+  if (mask_kind == NBMF_MASK_NONE) mask = nullptr;
+  const bool xbits = x_kind == NBMF_DATA_BITS, mbits = mask_kind == NBMF_MASK_BITS;
+  if (int rc = check_row_ld("ldx", ldx, xbits, c->n)) return rc;
+  if (mask)
+    if (int rc = check_row_ld("ldmask", ldmask, mbits, c->n)) return rc;
   if (!hist) return fail(NBMF_ERR_ARG, "null output");
   if (nrows > 0 && !x) return fail(NBMF_ERR_ARG, "null data");
   const size_t slots = 2 * (size_t)bins;
@@ -3760,21 +3859,24 @@ int nbmf_theta_hist(nbmf_ctx* c, int64_t row0, int64_t nrows, int bins, const ui
   if (int rc = set_device(c)) return rc;
   const long long n = c->n, ldp = panel_ld(c);
   RowPanels pl;
-  if (int rc = plan_row_panels(c, "nbmf_theta_hist", row0, nrows, (size_t)ldp * (mask ? 2 : 1), false, &pl)) return rc;
+  const size_t bit_bytes = (size_t)packed_ld(n) * ((xbits ? 1 : 0) + (mbits ? 1 : 0));   // the packed rows as they came
+  if (int rc = plan_row_panels(c, "nbmf_theta_hist", row0, nrows, (size_t)ldp * (mask ? 2 : 1) + bit_bytes, false, &pl)) return rc;
   PredictStage st{c->stream, {}};
-  unsigned char *x_d = nullptr, *m_d = nullptr;
+  unsigned char *x_d = nullptr, *m_d = nullptr, *xbits_d = nullptr, *mbits_d = nullptr;
   const int copies = (int)std::min<long long>(1024, std::max<long long>(1, env_int("NBMF_HIST_COPIES", 64)));
   unsigned long long *total_d = nullptr, *sum_d = nullptr;
   HIPCHK(st.get(&x_d, (size_t)pl.stage_rows() * ldp));
   if (mask) HIPCHK(st.get(&m_d, (size_t)pl.stage_rows() * ldp));
+  if (xbits) HIPCHK(st.get(&xbits_d, (size_t)pl.stage_rows() * packed_ld(n)));
+  if (mbits) HIPCHK(st.get(&mbits_d, (size_t)pl.stage_rows() * packed_ld(n)));
   HIPCHK(st.get(&total_d, sizeof(unsigned long long) * (slots + 2) * copies));
   HIPCHK(st.get(&sum_d, sizeof(unsigned long long) * (slots + 2)));
   HIPCHK(hipMemsetAsync(total_d, 0, sizeof(unsigned long long) * (slots + 2) * copies, c->stream));
   for (long long p0 = row0, pn; p0 < pl.end; p0 += pn) {
     pn = pl.rows_at(p0);
     const size_t done = (size_t)(p0 - row0);
-    HIPCHK(copy_rows(x_d, ldp, x + done * ldx, ldx, n, pn, hipMemcpyHostToDevice, c->stream));
-    if (mask) HIPCHK(copy_rows(m_d, ldp, mask + done * ldmask, ldmask, n, pn, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(stage_rows_as_bytes(xbits_d, (const char*)x + done * ldx, xbits, 1, ldx, n, pn, x_d, ldp, c->stream));
+    if (mask) HIPCHK(stage_rows_as_bytes(mbits_d, (const char*)mask + done * ldmask, mbits, 1, ldmask, n, pn, m_d, ldp, c->stream));
     HIPCHK(launch_hist_panel(c, pl, p0, pn, bins, x_d, m_d, copies, total_d));
     HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
   }
@@ -3798,9 +3900,19 @@ int nbmf_theta_hist(nbmf_ctx* c, int64_t row0, int64_t nrows, int bins, const ui
 int nbmf_rank_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, const int64_t* indptr, const int32_t* indices,
                    const uint8_t* exclude, int64_t ldx, int64_t* out_rank, int64_t* out_above, int64_t* out_tied, double* out_scores,
                    int64_t* out_eligible) {
+  return nbmf_rank_rows_v(c, row0, nrows, clip_theta, indptr, indices, exclude, NBMF_DATA_U8, ldx, out_rank, out_above, out_tied,
+                          out_scores, out_eligible);
+}
+
+int nbmf_rank_rows_v(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, const int64_t* indptr, const int32_t* indices,
+                     const void* exclude, int exclude_kind, int64_t ldx, int64_t* out_rank, int64_t* out_above, int64_t* out_tied,
+                     double* out_scores, int64_t* out_eligible) {
   if (int rc = predict_ready(c)) return rc;
   if (int rc = check_rows(c, row0, nrows)) return rc;
-  if (exclude && ldx < c->n) return fail(NBMF_ERR_ARG, "ldx %lld is less than n = %lld", (long long)ldx, (long long)c->n);
+  if (exclude_kind != NBMF_DATA_U8 && exclude_kind != NBMF_DATA_BITS) return fail(NBMF_ERR_ARG, "unknown exclude_kind %d", exclude_kind);
+  const bool exbits = exclude_kind == NBMF_DATA_BITS;
+  if (exclude)
+    if (int rc = check_row_ld("ldx", ldx, exbits, c->n)) return rc;
   if (nrows == 0) return NBMF_OK;
   if (!out_rank && !out_above && !out_tied && !out_scores && !out_eligible) return fail(NBMF_ERR_ARG, "no output requested");
   if (!indptr) return fail(NBMF_ERR_ARG, "null indptr");
@@ -3817,7 +3929,8 @@ int nbmf_rank_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, con
       return fail(NBMF_ERR_ARG, "target column %d at position %lld is outside [0, %lld)", (int)indices[p], (long long)p, n);
   if (int rc = set_device(c)) return rc;
   RowPanels pl;   // (the panel of nbmf_predict_rows, float64)
-  if (int rc = plan_row_panels(c, "nbmf_rank_rows", row0, nrows, (size_t)panel_ld(c) * sizeof(double), false, &pl)) return rc;
+  const size_t exb = exclude && exbits ? (size_t)packed_ld(n) : 0;   // a packed exclude row's share of the staging
+  if (int rc = plan_row_panels(c, "nbmf_rank_rows", row0, nrows, (size_t)panel_ld(c) * sizeof(double) + exb, false, &pl)) return rc;
   long long most = 1;   // targets of the fullest panel (1: no empty staging block)
   for (long long p0 = row0, pn; p0 < pl.end; p0 += pn) {
     pn = pl.rows_at(p0);
@@ -3829,7 +3942,7 @@ int nbmf_rank_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, con
   double *panel_d = nullptr, *scores_d = nullptr;
   long long *indptr_d = nullptr, *rank_d = nullptr, *above_d = nullptr, *tied_d = nullptr, *elig_d = nullptr;
   int* indices_d = nullptr;
-  unsigned char* ex_d = nullptr;
+  unsigned char *ex_d = nullptr, *exbits_d = nullptr;
   HIPCHK(st.get(&panel_d, sizeof(double) * rows * pl.ldp));
   HIPCHK(st.get(&indptr_d, sizeof(long long) * (rows + 1)));
   HIPCHK(st.get(&indices_d, sizeof(int) * (size_t)most));
@@ -3839,12 +3952,14 @@ int nbmf_rank_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, con
   if (out_scores) HIPCHK(st.get(&scores_d, sizeof(double) * (size_t)most));
   if (out_eligible) HIPCHK(st.get(&elig_d, sizeof(long long) * rows));
   if (exclude) HIPCHK(st.get(&ex_d, rows * n));
+  if (exb) HIPCHK(st.get(&exbits_d, rows * exb));
   for (long long p0 = row0, pn; p0 < pl.end; p0 += pn) {
     pn = pl.rows_at(p0);
     const size_t done = (size_t)(p0 - row0);
     const long long base = indptr[done];
     const size_t cnt = (size_t)(indptr[done + pn] - base);   // <= most
-    if (exclude) HIPCHK(copy_rows(ex_d, n, exclude + done * ldx, ldx, n, pn, hipMemcpyHostToDevice, c->stream));
+    if (exclude)
+      HIPCHK(stage_rows_as_bytes(exbits_d, (const char*)exclude + done * ldx, exbits, 1, ldx, n, pn, ex_d, n, c->stream));
     HIPCHK(hipMemcpyAsync(indptr_d, indptr + done, sizeof(long long) * (size_t)(pn + 1), hipMemcpyHostToDevice, c->stream));
     if (cnt) HIPCHK(hipMemcpyAsync(indices_d, indices + base, sizeof(int) * cnt, hipMemcpyHostToDevice, c->stream));
     HIPCHK(launch_theta_panel(c, pl, p0, pn, NBMF_PREDICT_F64, clip_theta, 0.0, panel_d));
@@ -4261,6 +4376,29 @@ int nbmf_selftest_unary(int device, int op, int n, const double* x, double* y) {
   HIPCHK(hipMemcpy(y, o, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
   dfree(d);
   dfree(o);
+  return NBMF_OK;
+}
+
+// unpack_bits_kernel on the caller's arrays (a test hook): `out` goes up whole, the kernel runs over it, and it comes back
+// whole, so a test sees every byte the kernel did not write.  All checks come before the first device call.
+int nbmf_selftest_unpack_bits(int device, const uint8_t* bits, int64_t ldbits, int64_t rows, int64_t n, uint8_t* out, int64_t ldout) {
+  if (!bits || !out) return fail(NBMF_ERR_ARG, "null bits or out");
+  if (rows < 0 || n < 0) return fail(NBMF_ERR_ARG, "rows and n must be >= 0 (got %lld and %lld)", (long long)rows, (long long)n);
+  if (ldbits < packed_ld(n))
+    return fail(NBMF_ERR_ARG, "ldbits %lld is less than ceil(n / 8) = %lld", (long long)ldbits, (long long)packed_ld(n));
+  if (ldout < n) return fail(NBMF_ERR_ARG, "ldout %lld is less than n = %lld", (long long)ldout, (long long)n);
+  if (rows == 0 || n == 0) return NBMF_OK;
+  HIPCHK(hipSetDevice(device));
+  // (bits ends with the last byte of its last row; out is rows x ldout bytes, all of them the caller's)
+  const size_t bits_bytes = (size_t)(rows - 1) * ldbits + (size_t)packed_ld(n), out_bytes = (size_t)rows * ldout;
+  PredictStage st{nullptr, {}};   // (a self-test entry, no context: the null stream)
+  unsigned char *bits_d = nullptr, *out_d = nullptr;
+  HIPCHK(st.get(&bits_d, bits_bytes));
+  HIPCHK(st.get(&out_d, out_bytes));
+  HIPCHK(hipMemcpy(bits_d, bits, bits_bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(out_d, out, out_bytes, hipMemcpyHostToDevice));
+  HIPCHK(launch_unpack_bits(bits_d, ldbits, rows, n, out_d, ldout, nullptr));
+  HIPCHK(hipMemcpy(out, out_d, out_bytes, hipMemcpyDeviceToHost));
   return NBMF_OK;
 }
 

@@ -23,15 +23,19 @@ that end in a synchronise (the library's predict calls do; NumPy's are synchrono
       entries observed by the fit, the unobserved 10 % (and the 1 % of them with the largest draw) held out as index
       pairs -- Context.eval_loglik on the training context against the route there was before it (get_factors, then
       set_factors into a second context that holds the data under the dense held-out mask, then loglik_strict), and a
-      50-iteration fit with an evaluation every 10 iterations against the same fit without an eval set.
+      50-iteration fit with an evaluation every 10 iterations against the same fit without an eval set;
+  (h) the calls that upload binary operands, from bit-packed ones (``PackedBits``: one bit per entry over PCIe, unpacked on
+      the device) beside the same call from uint8 -- ``score_samples_bits`` (rows and columns, 90 % mask), ``theta_hist_bits``
+      (256 bins, the same data and mask) and ``top_n_bits`` (N = 10, a 10 %-dense exclude) -- on one set of data of the legs'
+      own stream, the packed result checked for equality with the uint8 one before any time is taken.
 
 The host legs are the comparison; the device path is never its own yardstick.  Before any time is taken the device and host
 results are compared at these sizes within tests/test_gpu_predict.py's bound, 2.1 K 2^-53 (|W| @ |H|) per entry; the
 ranking is compared exactly with the host selection over the device's own slab (the shape has no ties); the score sums are
 compared with the host's over the device's own slab within tests/test_gpu_score_samples.py's bound plus NumPy's own
 summation error; the class histograms and the ranks are compared for EQUALITY with NumPy's over the device's own slab.
-``--legs`` picks the legs to time (default: the first four; ``theta_hist``, ``rank_of`` and ``eval_curve`` are asked for by
-name; ``eval_curve`` alone skips the factors-only context and its agreement checks).
+``--legs`` picks the legs to time (default: the first four; ``theta_hist``, ``rank_of``, ``eval_curve`` and the ``*_bits`` legs are
+asked for by name; ``eval_curve`` alone skips the factors-only context and its agreement checks).
 Prints progress lines and, last, ONE JSON line.  Needs an MI355X: there is no CPU fallback."""
 import argparse
 import json
@@ -51,12 +55,14 @@ ap.add_argument("--pairs", type=int, default=1 << 22)
 ap.add_argument("--rows", type=int, default=8192)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--legs", default="pairs,slabs,top_n,score_samples",
-                help="comma-separated: pairs, slabs, top_n, score_samples, theta_hist, rank_of, eval_curve")
+                help="comma-separated: pairs, slabs, top_n, score_samples, theta_hist, rank_of, eval_curve, score_samples_bits, "
+                     "theta_hist_bits, top_n_bits")
 ap.add_argument("--device-only", action="store_true",
                 help="theta_hist, rank_of: skip the timed host legs (for a kernel trace of the device legs)")
 args = ap.parse_args()
 legs = set(args.legs.split(","))
-assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist", "rank_of", "eval_curve"}, f"unknown leg in {args.legs}"
+BITS_LEGS = {"score_samples_bits", "theta_hist_bits", "top_n_bits"}
+assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist", "rank_of", "eval_curve"} | BITS_LEGS, f"unknown leg in {args.legs}"
 m, n, k, P, R = args.m, args.n, args.k, args.pairs, min(args.rows, args.m)
 
 
@@ -293,6 +299,39 @@ with _hip.Context(m, n, k) as ctx:
         d["upload_share_estimated"] = min(1.0, 2.0 * max(0.0, d["device_s"] - d["device_no_mask_s"]) / d["device_s"])
         d["speedup_vs_predict_rows_then_host"] = d["predict_rows_then_host_s"] / d["device_s"]
         res["score_samples_leg"] = d
+
+    # ---- (h) the uploading calls from bit-packed operands, beside the same call from uint8 ----------------------------------------
+    if legs & BITS_LEGS:
+        from nbmf_mm_amd import PackedBits
+        gb = np.random.default_rng(2028)                    # (its own stream: the same data whichever legs ran before)
+        X = gb.random((R, n)) < 0.25
+        mask = gb.random((R, n)) < 0.90
+        excl = gb.random((R, n)) < 0.10
+        PX, PM, PE = (PackedBits.from_dense(a) for a in (X, mask, excl))
+        h = {"observed": float(mask.mean()), "exclude_density": float(excl.mean()), "uint8_bytes_per_operand": R * n,
+             "packed_bytes_per_operand": PX.nbytes}
+
+        def both(name, from_uint8, from_bits):
+            want, got = from_uint8(), from_bits()
+            assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(want, got)), f"{name}: packed and uint8 input disagree"
+            t = {}
+            t["uint8_s"], t["uint8_all_s"] = median_s(from_uint8)
+            t["bits_s"], t["bits_all_s"] = median_s(from_bits)
+            t["bits_over_uint8"] = t["bits_s"] / t["uint8_s"]
+            say(f"{name}: uint8 {t['uint8_s']:.6f} s, bits {t['bits_s']:.6f} s")
+            return t
+
+        if "score_samples_bits" in legs:
+            h["score_samples"] = both("score_rows rows + cols", lambda: ctx.score_rows(X, mask, 0, R, rows=True, cols=True),
+                                      lambda: ctx.score_rows(PX, PM, 0, R, rows=True, cols=True))
+        if "theta_hist_bits" in legs:
+            h["theta_hist_256"] = both("theta_hist 256 bins", lambda: ctx.theta_hist(X, mask, 0, R, bins=256),
+                                       lambda: ctx.theta_hist(PX, PM, 0, R, bins=256))
+        if "top_n_bits" in legs:
+            h["top_n_10_exclude"] = both("top_n N=10 exclude", lambda: ctx.top_n(10, 0, R, exclude=excl),
+                                         lambda: ctx.top_n(10, 0, R, exclude=PE))
+        res["packed_bits_leg"] = h
+        del X, mask, excl, PX, PM, PE
 
     # ---- (f) ranks of held-out entries (before (e), which changes the factors) ---------------------------------------------------
     if "rank_of" in legs:
