@@ -246,6 +246,26 @@ int nbmf_predict_at(nbmf_ctx* ctx, const int64_t* rows, const int64_t* cols, int
 int nbmf_predict_rows(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int clip_theta, int out_kind,
                       double threshold, void* out, int64_t ldout);
 
+/* A yes / no decision per entry of Theta for rows [row0, row0 + nrows) and all n columns, returned as bits: entry j of row
+ * i is bit 7 - j % 8 of out[(i - row0) * ldout + j / 8] (np.packbits(..., axis=1); the layout of NBMF_DATA_BITS, so the result
+ * is an operand of every call that takes bits).  theta[i, j] is bit for bit the entry nbmf_predict_rows(..., clip_theta,
+ * NBMF_PREDICT_F64, ...) returns, and the decision is
+ * NBMF_BITS_THRESHOLD: theta > threshold, strictly: the bits of nbmf_predict_rows' NBMF_PREDICT_U8 bytes; `seed` is ignored.
+ * NBMF_BITS_SAMPLE:    u < theta: one draw of X ~ Bernoulli(Theta), with the counter-based uniform of nbmf_generate at
+ *                      row0 = col0 = 0: u = (splitmix64(seed * 0x100000001B3 + i * n + j) >> 11) * 2^-53, in [0, 1), the
+ *                      arithmetic modulo 2^64.  theta = 0 never draws a one and theta >= 1 always does; `threshold` is
+ *                      ignored.  The host can regenerate any u (nbmf_mm_amd._hip.hash_uniform does).
+ * A NaN theta decides 0 in both modes.  Exactly ceil(n / 8) bytes of each output row are written, whatever ldout (bytes,
+ * >= ceil(n / 8)) is, and the pad bits of a row's last byte are written as zeros.  A row's bits depend on the factors, the
+ * mode's argument and its own row and column numbers only: not on row0, on the panels (NBMF_PREDICT_PANEL_ROWS, as above;
+ * a panel row stages nA / 8 bytes) or on other rows; the same call twice gives the same bytes.  NBMF_ERR_ARG for an unknown
+ * mode, a NaN threshold in threshold mode, ldout < ceil(n / 8), rows outside [0, m), or a NULL out with nrows > 0;
+ * nrows == 0 touches nothing.  Same state rules and synchronisation as nbmf_predict_rows. */
+#define NBMF_BITS_THRESHOLD 0
+#define NBMF_BITS_SAMPLE 1
+int nbmf_theta_bits(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int clip_theta, int mode,
+                    double threshold, uint64_t seed, uint8_t* out, int64_t ldout);
+
 /* The `top` columns with the largest Theta in each of the rows [row0, row0 + nrows), ranked on the device: for every
  * row i and slot s < top, out_cols[(i - row0) * ldout + s] is the s-th column in the order "Theta descending (compared
  * numerically), ties by ascending column" over the ELIGIBLE columns of the row, and out_scores (may be NULL) its Theta.

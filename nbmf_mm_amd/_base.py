@@ -10,8 +10,8 @@ from sklearn.utils import check_array
 
 from . import _hip, _metrics
 from ._packed import PackedBits
-from ._solver import (device_predict, device_rank_of, device_score, device_score_samples, device_theta_hist, device_top_n,
-                      eval_pairs, nbmf_mm_restarts, nbmf_mm_solver, w_only_transform)
+from ._solver import (device_predict, device_rank_of, device_score, device_score_samples, device_theta_bits, device_theta_hist,
+                      device_top_n, eval_pairs, nbmf_mm_restarts, nbmf_mm_solver, w_only_transform)
 from ._utils import check_is_fitted
 
 # Accepted spellings of the two orientations: the exact strings of src/nbmf_mm/_base.py:127-137
@@ -273,13 +273,42 @@ class NBMFMM(BaseEstimator, TransformerMixin):
             rows, cols = _hip.index_pairs(rows, cols)
         return device_predict(W, H, rows=rows, cols=cols, device=self.device)
 
-    def predict(self, W=None, threshold=0.5):
-        """The bool matrix ``predict_proba(W) > threshold``, compared on the device: one byte per entry comes back."""
+    def predict(self, W=None, threshold=0.5, packed=False):
+        """The bool matrix ``predict_proba(W) > threshold``, compared on the device: one byte per entry comes back.  With
+        ``packed=True`` one BIT per entry comes back: a :class:`PackedBits` of shape ``(W.shape[0], n_features)`` whose
+        ``toarray()`` is that bool matrix, an eighth of its host memory."""
+        if not isinstance(packed, (bool, np.bool_)):
+            raise ValueError(f"packed must be a bool (got {packed!r})")
         W, H = self._prediction_factors(W)
         threshold = float(threshold)
         if np.isnan(threshold):
             raise ValueError("threshold is NaN")
+        if packed:
+            return device_theta_bits(W, H, threshold=threshold, device=self.device)
         return device_predict(W, H, threshold=threshold, device=self.device)
+
+    def sample(self, W=None, random_state=None, packed=False):
+        """One draw ``X_rep ~ Bernoulli(predict_proba(W))`` of the fitted model, made on the device (``W`` defaulting to
+        ``W_``): a bool ``(W.shape[0], n_features)`` array, or with ``packed=True`` the :class:`PackedBits` the device
+        produced (the dense form is its ``toarray()``), which ``fit``, ``score_samples``, ``theta_histogram`` and
+        ``top_n(exclude=)`` take as it is.
+
+        The draw is counter-based: ``X_rep[i, j] = u[i, j] < predict_proba(W)[i, j]`` with
+        ``u[i, j] = (splitmix64(seed * 0x100000001B3 + i * n_features + j) >> 11) * 2**-53`` (arithmetic modulo 2**64;
+        ``_hip.hash_uniform(W.shape[0], n_features, seed)`` is that matrix, or any entries of it), so any entry can be
+        regenerated on the host.  ``random_state``: the seed, an int in ``[0, 2**64)``, or None for one drawn from NumPy's
+        global RNG.  The result is deterministic in ``(W, components_, random_state)``; different seeds give independent
+        matrices.  An entry with probability 0 is never drawn, one with probability 1 always is.
+
+        Uses: posterior-predictive checks (replicated row and column sums against the data's:
+        examples/posterior_predictive.py), a parametric bootstrap -- ``NBMF(...).fit(model.sample(packed=True))`` --, and
+        planted benchmark data from known factors."""
+        if not isinstance(packed, (bool, np.bool_)):
+            raise ValueError(f"packed must be a bool (got {packed!r})")
+        seed = _hip.sample_seed(random_state)
+        W, H = self._prediction_factors(W)
+        bits = device_theta_bits(W, H, seed=seed, device=self.device)
+        return bits if packed else bits.toarray()
 
     def top_n(self, n=10, W=None, exclude=None):
         """The ``n`` most probable features of every row of ``W`` (default ``W_``), ranked on the GPU: ``(cols, scores)``,

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, byref, c_char_p, c_double, c_int, c_int64, c_void_p
+from ctypes import POINTER, byref, c_char_p, c_double, c_int, c_int64, c_uint64, c_void_p
 
 import numpy as np
 
@@ -42,9 +42,11 @@ SYMBOLS = [
     "nbmf_predict_at", "nbmf_predict_rows", "nbmf_top_n", "nbmf_score_rows", "nbmf_theta_hist",
     "nbmf_rank_rows", "nbmf_set_eval", "nbmf_eval_loglik", "nbmf_get_eval", "nbmf_get_best_factors",
     "nbmf_top_n_v", "nbmf_score_rows_v", "nbmf_theta_hist_v", "nbmf_rank_rows_v", "nbmf_selftest_unpack_bits",
+    "nbmf_theta_bits",
 ]
 DATA_F64, DATA_U8, DATA_F32, DATA_BITS = 0, 1, 2, 3
 PREDICT_F64, PREDICT_U8 = 0, 1
+BITS_THRESHOLD, BITS_SAMPLE = 0, 1
 TOP_N_MAX = 256
 HIST_MAX_BINS = 1024
 
@@ -194,6 +196,7 @@ def load():
     lib.nbmf_rank_rows_v.argtypes = [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p]
     lib.nbmf_selftest_unpack_bits.argtypes = [c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64]
+    lib.nbmf_theta_bits.argtypes = [c_void_p, c_int64, c_int64, c_int, c_int, c_double, c_uint64, c_void_p, c_int64]
     lib.nbmf_set_eval.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int]
     lib.nbmf_eval_loglik.argtypes = [c_void_p, dp]
     lib.nbmf_get_eval.argtypes = [c_void_p, c_int, POINTER(c_int), c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]
@@ -631,6 +634,31 @@ class Context:
                                            float(threshold) if byte_kind else 0.0, out.ctypes.data_as(c_void_p), ld))
         return out
 
+    def theta_bits(self, row0=0, nrows=None, *, threshold=None, seed=None, clip_theta=True, out=None):
+        """A yes / no decision per entry of Theta for rows ``[row0, row0 + nrows)`` and all n columns, decided and packed
+        on the device (``nbmf_theta_bits``): a :class:`PackedBits` of shape ``(nrows, n)`` -- one bit per entry comes back.
+        Exactly one of ``threshold`` (the bits of ``predict_rows(threshold=...)``: ``Theta > threshold``, strictly) and
+        ``seed`` (an int in ``[0, 2**64)``: one draw of Bernoulli(Theta), ``hash_uniform(m, n, seed) < Theta``) is given.
+        ``out``, if given, receives the bytes and backs the result: a uint8 array of shape ``(nrows, ceil(n / 8))``, unit
+        stride along a row and any row stride of at least ``ceil(n / 8)`` bytes -- a slice of a wider array is fine, and
+        nothing outside the slice is touched.  The pad bits of a row's last byte are zeros: ``.bits`` equals
+        ``np.packbits(dense, axis=1)``."""
+        row0, nrows = self._rows(row0, nrows)
+        if (threshold is None) == (seed is None):
+            raise ValueError("give exactly one of threshold and seed")
+        if seed is not None:
+            seed = sample_seed(seed)
+        nb = (self.n + 7) // 8
+        if out is None:
+            out = np.empty((nrows, nb), dtype=np.uint8)
+        elif not isinstance(out, np.ndarray):
+            raise ValueError(f"out must be a NumPy array: it is written in place (got {type(out).__name__})")
+        ld = row_array(out, nrows, nb, "out", (np.uint8,))[2]
+        _check(self._lib.nbmf_theta_bits(self._h, row0, nrows, int(bool(clip_theta)), BITS_THRESHOLD if seed is None else BITS_SAMPLE,
+                                         0.0 if threshold is None else float(threshold), seed or 0,
+                                         out.ctypes.data_as(c_void_p), ld))
+        return PackedBits(out, (nrows, self.n))
+
     def top_n(self, top, row0=0, nrows=None, exclude=None, clip_theta=True, return_scores=True):
         """The ``top`` columns with the largest Theta in each of the rows ``[row0, row0 + nrows)``, ranked on the device
         (``nbmf_top_n``): ``(cols, scores)``, ``cols`` int64 ``(nrows, top)`` and ``scores`` float64 of the same shape (None
@@ -885,11 +913,10 @@ def selftest_unpack_bits(bits, n, out, device=0):
     return out
 
 
-def synthetic_reference(m, n, seed, density=0.25, observed=1.0, rows=None, cols=None):
-    """NumPy regeneration of ``Context.generate`` (same splitmix64 hash of (seed, i*n + j)): returns
-    (Y float64, mask bool) of the m x n matrix, or of its sub-matrix ``[rows][:, cols]`` when index
-    arrays are given (entries are hashed independently, so a slice costs only its own size).
-    For the tests; O(rows * cols) host memory."""
+def _hash_u01(m, n, seed, rows, cols, salt=0):
+    """A uniform of the device's counter-based generator (``synth_code`` in nbmf_pack_kernels.inc) for the m x n matrix or
+    its sub-matrix ``[rows][:, cols]``: the top 53 bits of splitmix64 of ``(seed * 0x100000001B3 + i * n + j) ^ salt``
+    (arithmetic modulo 2^64) times 2^-53."""
     def mix(x):
         x = (x + np.uint64(0x9E3779B97F4A7C15)).astype(np.uint64)
         x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
@@ -900,6 +927,35 @@ def synthetic_reference(m, n, seed, density=0.25, observed=1.0, rows=None, cols=
     with np.errstate(over="ignore"):
         idx = ri[:, None] * np.uint64(n) + ci[None, :]
         base = np.uint64(seed) * np.uint64(0x100000001B3) + idx
-        u = (mix(base) >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
-        v = (mix(base ^ np.uint64(0xD6E8FEB86659FD93)) >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+        return (mix(base ^ np.uint64(salt)) >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+
+
+def hash_uniform(m, n, seed, rows=None, cols=None):
+    """The uniforms in [0, 1) that ``Context.generate`` and ``Context.theta_bits(seed=...)`` compare against, regenerated in
+    NumPy: ``u[i, j] = (splitmix64(seed * 0x100000001B3 + i * n + j) >> 11) * 2**-53``, the arithmetic modulo 2**64, as a
+    float64 ``(m, n)`` matrix, or its sub-matrix ``[rows][:, cols]`` when index arrays are given (entries are hashed
+    independently, so a slice costs only its own size).  ``seed``: an int in ``[0, 2**64)``."""
+    return _hash_u01(m, n, seed, rows, cols)
+
+
+def synthetic_reference(m, n, seed, density=0.25, observed=1.0, rows=None, cols=None):
+    """NumPy regeneration of ``Context.generate`` (same splitmix64 hash of (seed, i*n + j): :func:`hash_uniform`): returns
+    (Y float64, mask bool) of the m x n matrix, or of its sub-matrix ``[rows][:, cols]`` when index
+    arrays are given (entries are hashed independently, so a slice costs only its own size).
+    For the tests; O(rows * cols) host memory."""
+    u = hash_uniform(m, n, seed, rows, cols)
+    v = _hash_u01(m, n, seed, rows, cols, salt=0xD6E8FEB86659FD93)      # the observed-or-not uniform of the same entry
     return (u < density).astype(np.float64), v < observed
+
+
+def sample_seed(random_state):
+    """The 64-bit seed of ``theta_bits(seed=...)`` / ``NBMF.sample`` from a ``random_state``, without a device: an int
+    (not a bool) in ``[0, 2**64)`` is used as it is; ``None`` draws one from NumPy's global RNG, as ``transform`` draws its
+    start.  Raises ``ValueError`` for anything else."""
+    if random_state is None:
+        return int.from_bytes(np.random.bytes(8), "little")
+    if isinstance(random_state, (bool, np.bool_)) or not isinstance(random_state, (int, np.integer)):
+        raise ValueError(f"random_state must be None or an integer in [0, 2**64) (got {random_state!r})")
+    if not 0 <= int(random_state) < 2 ** 64:
+        raise ValueError(f"random_state must be in [0, 2**64) (got {int(random_state)})")
+    return int(random_state)

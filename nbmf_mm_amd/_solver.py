@@ -352,6 +352,15 @@ def device_predict(W, H, rows=None, cols=None, threshold=None, device=0):
         return ctx.predict_rows(0, m, clip_theta=True, threshold=threshold)
 
 
+def device_theta_bits(W, H, threshold=None, seed=None, device=0):
+    """A decision per entry of Theta = clip(``W @ H``, 0, 1), made and bit-packed on the GPU (``Context.theta_bits``): the
+    :class:`PackedBits` of ``Theta > threshold``, or with a ``seed`` (already validated: ``_hip.sample_seed``) of one draw
+    ``_hip.hash_uniform(rows, features, seed) < Theta`` of Bernoulli(Theta).  ``W``, ``H`` as in :func:`device_predict`.
+    One bit per entry comes back.  Factors only: no data is uploaded."""
+    with _factors_only(W, H, device) as (ctx, m, n):
+        return ctx.theta_bits(0, m, threshold=threshold, seed=seed, clip_theta=True)
+
+
 #: bytes of densified ``exclude`` that :func:`device_top_n` holds at a time (one row block)
 TOP_N_EXCLUDE_BLOCK_BYTES = 64 << 20
 

@@ -325,6 +325,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 #include "nbmf_rank_kernels.inc"
 #include "nbmf_eval_kernels.inc"
 #include "nbmf_bits_kernels.inc"
+#include "nbmf_theta_bits_kernels.inc"
 
 }  // namespace
 
@@ -2544,8 +2545,8 @@ int one_shot(nbmf_ctx* c, bool with_prior, int strict, int clip, bool collect_ti
 // (also the single-launch engine's end-of-run guard: small_guard)
 int loss_by_launches(nbmf_ctx* c, double* loss) { return one_shot(c, /*with_prior=*/true, 0, 0, /*collect_timing=*/true, loss); }
 
-// ---- shared by the six entry points that read Theta back: nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows,
-// nbmf_theta_hist, nbmf_rank_rows
+// ---- shared by the seven entry points that read Theta back: nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows,
+// nbmf_theta_hist, nbmf_rank_rows, nbmf_theta_bits
 // (DESIGN.md 4.6).  Staging of one such call, from the pool: given back when the call returns, on every path, after the
 // stream has drained (a pooled block may be handed to the next caller at once).
 struct PredictStage {
@@ -2572,7 +2573,7 @@ int predict_ready(nbmf_ctx* c) {
   return NBMF_OK;
 }
 
-int check_rows(nbmf_ctx* c, int64_t row0, int64_t nrows) {   // the five row-slab entry points: all but nbmf_predict_at
+int check_rows(nbmf_ctx* c, int64_t row0, int64_t nrows) {   // the six row-slab entry points: all but nbmf_predict_at
   if (nrows < 0 || row0 < 0 || row0 > c->m || nrows > c->m - row0)
     return fail(NBMF_ERR_ARG, "rows [%lld, %lld + %lld) are not inside [0, %lld)", (long long)row0, (long long)row0, (long long)nrows,
                 (long long)c->m);
@@ -2687,7 +2688,7 @@ hipError_t launch_hist_panel(nbmf_ctx* c, const RowPanels& pl, long long p0, lon
 // ------------------------------------------------------------------------------------------
 extern "C" {
 
-int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows, nbmf_theta_hist, nbmf_rank_rows, nbmf_set_eval, nbmf_eval_loglik, nbmf_get_eval, nbmf_get_best_factors: compatible additions, which a caller detects by the symbol
+int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows, nbmf_theta_hist, nbmf_rank_rows, nbmf_set_eval, nbmf_eval_loglik, nbmf_get_eval, nbmf_get_best_factors, the *_v forms and nbmf_selftest_unpack_bits, nbmf_theta_bits: compatible additions, which a caller detects by the symbol
 // The sources this binary was compiled from: first 12 hex digits of the SHA-256 over nbmf_hip.hip, the *.inc files (sorted
 // by name) and include/nbmf_hip.h, put in by the Makefile (tools/src_hash.sh prints the same for the tree).  A profile or a
 // bench line that quotes it can be tied to a commit; a library built by hand without the Makefile says "unstamped".
@@ -3671,6 +3672,40 @@ int nbmf_predict_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, 
     HIPCHK(launch_theta_panel(c, pl, p0, pn, out_kind, clip_theta, threshold, panel_d));
     HIPCHK(copy_rows((char*)out + (size_t)(p0 - row0) * ldout * elt, ldout * elt, panel_d, pl.ldp * elt, c->n * elt, pn,
                      hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
+  }
+  return NBMF_OK;
+}
+
+// ---- Theta decided per entry, as bits (theta_bits_kernel in nbmf_theta_bits_kernels.inc) ---------------------
+// The shape of nbmf_predict_rows: per panel one launch into a staging panel of nA / 8 bytes per row (a multiple of 16: the
+// kernel stores 8 aligned bytes per wave and row), then ceil(n / 8) bytes of each row back to the caller.
+int nbmf_theta_bits(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, int mode, double threshold, uint64_t seed,
+                    uint8_t* out, int64_t ldout) {
+  if (int rc = predict_ready(c)) return rc;
+  if (int rc = check_rows(c, row0, nrows)) return rc;
+  if (int rc = check_row_ld("ldout", ldout, true, c->n)) return rc;
+  if (mode != NBMF_BITS_THRESHOLD && mode != NBMF_BITS_SAMPLE) return fail(NBMF_ERR_ARG, "unknown mode %d", mode);
+  if (mode == NBMF_BITS_THRESHOLD && threshold != threshold) return fail(NBMF_ERR_ARG, "threshold is NaN");
+  if (nrows == 0) return NBMF_OK;
+  if (!out) return fail(NBMF_ERR_ARG, "null output");
+  if (int rc = set_device(c)) return rc;
+  const long long ldb = (long long)c->nA / 8;   // (nA is a multiple of 128)
+  RowPanels pl;
+  if (int rc = plan_row_panels(c, "nbmf_theta_bits", row0, nrows, (size_t)ldb, false, &pl)) return rc;
+  PredictStage st{c->stream, {}};
+  unsigned char* panel_d = nullptr;
+  HIPCHK(st.get(&panel_d, (size_t)pl.stage_rows() * ldb));
+  const size_t width = (size_t)packed_ld(c->n);
+  for (long long p0 = row0, pn; p0 < pl.end; p0 += pn) {
+    pn = pl.rows_at(p0);
+    hipLaunchKernelGGL(mode == NBMF_BITS_SAMPLE ? theta_bits_kernel<TB_SAMPLE> : theta_bits_kernel<TB_THRESHOLD>, pl.grid(p0, pn),
+                       dim3(PR_WAVES * 64), 0, c->stream, (const double*)c->Wn, (const double*)c->Hn, c->k, (long long)c->mA,
+                       (long long)c->nA, (long long)c->n, p0, pn, ldb, clip_theta != 0 ? 1 : 0, threshold,
+                       (unsigned long long)seed, panel_d);
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_rows(out + (size_t)(p0 - row0) * ldout, (size_t)ldout, panel_d, (size_t)ldb, width, pn, hipMemcpyDeviceToHost,
+                     c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
   }
   return NBMF_OK;

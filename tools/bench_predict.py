@@ -27,7 +27,12 @@ that end in a synchronise (the library's predict calls do; NumPy's are synchrono
   (h) the calls that upload binary operands, from bit-packed ones (``PackedBits``: one bit per entry over PCIe, unpacked on
       the device) beside the same call from uint8 -- ``score_samples_bits`` (rows and columns, 90 % mask), ``theta_hist_bits``
       (256 bins, the same data and mask) and ``top_n_bits`` (N = 10, a 10 %-dense exclude) -- on one set of data of the legs'
-      own stream, the packed result checked for equality with the uint8 one before any time is taken.
+      own stream, the packed result checked for equality with the uint8 one before any time is taken;
+  (i) decisions per entry of those rows leaving the device as bits (``Context.theta_bits``): ``predict_bits`` -- Theta > 0.5
+      as a ``PackedBits`` beside the thresholded bytes of (b) in the same process, the two differing in the bytes that cross
+      PCIe (1/8) -- and ``sample`` -- one draw of Bernoulli(Theta) against the host route there was before it
+      (predict_rows float64, ``default_rng().random(...) <``, ``np.packbits``).  The bits are checked for equality with
+      np.packbits of the byte slab, and with ``hash_uniform < `` the device's own float64 slab, before any time is taken.
 
 The host legs are the comparison; the device path is never its own yardstick.  Before any time is taken the device and host
 results are compared at these sizes within tests/test_gpu_predict.py's bound, 2.1 K 2^-53 (|W| @ |H|) per entry; the
@@ -35,7 +40,7 @@ ranking is compared exactly with the host selection over the device's own slab (
 compared with the host's over the device's own slab within tests/test_gpu_score_samples.py's bound plus NumPy's own
 summation error; the class histograms and the ranks are compared for EQUALITY with NumPy's over the device's own slab.
 ``--legs`` picks the legs to time (default: the first four; ``theta_hist``, ``rank_of``, ``eval_curve`` and the ``*_bits`` legs are
-asked for by name; ``eval_curve`` alone skips the factors-only context and its agreement checks).
+asked for by name, as are ``predict_bits`` and ``sample``; ``eval_curve`` alone skips the factors-only context and its agreement checks).
 Prints progress lines and, last, ONE JSON line.  Needs an MI355X: there is no CPU fallback."""
 import argparse
 import json
@@ -56,13 +61,14 @@ ap.add_argument("--rows", type=int, default=8192)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--legs", default="pairs,slabs,top_n,score_samples",
                 help="comma-separated: pairs, slabs, top_n, score_samples, theta_hist, rank_of, eval_curve, score_samples_bits, "
-                     "theta_hist_bits, top_n_bits")
+                     "theta_hist_bits, top_n_bits, predict_bits, sample")
 ap.add_argument("--device-only", action="store_true",
-                help="theta_hist, rank_of: skip the timed host legs (for a kernel trace of the device legs)")
+                help="theta_hist, rank_of, predict_bits, sample: skip the timed host legs (for a kernel trace of the device legs)")
 args = ap.parse_args()
 legs = set(args.legs.split(","))
 BITS_LEGS = {"score_samples_bits", "theta_hist_bits", "top_n_bits"}
-assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist", "rank_of", "eval_curve"} | BITS_LEGS, f"unknown leg in {args.legs}"
+DECISION_LEGS = {"predict_bits", "sample"}
+assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist", "rank_of", "eval_curve"} | BITS_LEGS | DECISION_LEGS, f"unknown leg in {args.legs}"
 m, n, k, P, R = args.m, args.n, args.k, args.pairs, min(args.rows, args.m)
 
 
@@ -332,6 +338,46 @@ with _hip.Context(m, n, k) as ctx:
                                          lambda: ctx.top_n(10, 0, R, exclude=PE))
         res["packed_bits_leg"] = h
         del X, mask, excl, PX, PM, PE
+
+    # ---- (i) decisions per entry as bits: Theta > 0.5, and one draw of Bernoulli(Theta) ---------------------------------------------
+    if legs & DECISION_LEGS:
+        nb = (n + 7) // 8
+        outb = np.empty((R, nb), dtype=np.uint8)
+        i = {"packed_output_bytes": R * nb, "u8_output_bytes": R * n}
+        if "predict_bits" in legs:
+            ctx.predict_rows(0, R, threshold=0.5, out=out8)
+            ctx.theta_bits(0, R, threshold=0.5, out=outb)
+            assert np.array_equal(outb, np.packbits(out8, axis=1)), "theta_bits(threshold) is not the packed byte slab"
+            t = {}
+            t["device_u8_s"], t["device_u8_all_s"] = median_s(lambda: ctx.predict_rows(0, R, threshold=0.5, out=out8))
+            t["device_bits_s"], t["device_bits_all_s"] = median_s(lambda: ctx.theta_bits(0, R, threshold=0.5, out=outb))
+            say(f"predict: bytes {t['device_u8_s']:.6f} s, bits {t['device_bits_s']:.6f} s")
+            t["bits_over_u8"] = t["device_bits_s"] / t["device_u8_s"]
+            t["bits_faster_end_to_end"] = bool(t["device_bits_s"] < t["device_u8_s"])
+            if not args.device_only:
+                t["u8_then_packbits_s"], t["u8_then_packbits_all_s"] = median_s(
+                    lambda: np.packbits(ctx.predict_rows(0, R, threshold=0.5, out=out8), axis=1))
+                say(f"predict: bytes + np.packbits {t['u8_then_packbits_s']:.6f} s")
+            i["predict_bits"] = t
+        if "sample" in legs:
+            seed = 2029
+            ctx.predict_rows(0, R, out=out64)
+            ctx.theta_bits(0, R, seed=seed, out=outb)
+            want = _hip.hash_uniform(m, n, seed, rows=np.arange(R)) < out64
+            assert np.array_equal(outb, np.packbits(want, axis=1)), "theta_bits(seed) is not hash_uniform < predict_rows"
+            t = {"ones": float(want.mean())}
+            del want
+            t["device_s"], t["device_all_s"] = median_s(lambda: ctx.theta_bits(0, R, seed=seed, out=outb))
+            say(f"sample: device {t['device_s']:.6f} s")
+            if not args.device_only:
+                gs = np.random.default_rng(2029)            # (its own stream)
+                t["predict_rows_then_host_s"], t["predict_rows_then_host_all_s"] = median_s(
+                    lambda: np.packbits(gs.random((R, n)) < ctx.predict_rows(0, R, out=out64), axis=1))
+                say(f"sample: predict_rows + default_rng().random < + np.packbits {t['predict_rows_then_host_s']:.6f} s")
+                t["speedup_vs_predict_rows_then_host"] = t["predict_rows_then_host_s"] / t["device_s"]
+            i["sample"] = t
+        res["decision_bits_leg"] = i
+        del outb
 
     # ---- (f) ranks of held-out entries (before (e), which changes the factors) ---------------------------------------------------
     if "rank_of" in legs:
