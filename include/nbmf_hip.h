@@ -423,6 +423,41 @@ int nbmf_eval_loglik(nbmf_ctx* ctx, double* loglik);
 int nbmf_get_eval(nbmf_ctx* ctx, int cap, int* n_evals, int* iters, double* logliks, int* best_iter, int* stopped_early);
 int nbmf_get_best_factors(nbmf_ctx* ctx, double* W_kxm, double* H_kxn);
 
+/* The held-out split drawn on the device: the eval set is taken out of the data the context holds, no mask and no index
+ * list crossing from the host, and can be put back so that the next fold of a cross-validation needs no upload.  No
+ * reference counterpart (examples/reproduce_magron2022.py:26-38 loads ready-made train / val / test masks from a file).
+ * THE RULE.  The entry at row u, column v of the USER's matrix (U x V; the internal matrix, or its transpose when
+ * transposed != 0, as under nbmf_upload) has the counter idx = u * V + v and the uniform
+ *   unif = (splitmix64((seed * 0x100000001B3 + idx) ^ 0xA0761D6478BD642F) >> 11) * 2^-53,   arithmetic modulo 2^64:
+ * the uniform of nbmf_generate / nbmf_theta_bits with a salt of its own, so a split with the seed a sample was drawn with is
+ * another draw.  The entry is HELD OUT iff it is observed and lo <= unif < hi (compared as the 53-bit integers: exact).
+ * The same (seed, shape of the user's matrix) gives the same split under both orientations, and the intervals
+ * [f / k, (f + 1) / k), f = 0 .. k - 1, partition the observed entries.
+ * nbmf_hold_out: every held-out entry becomes "valid, unobserved" in both images, and the list of them -- (row, col) in
+ * INTERNAL coordinates, truth 1 for an observed one and 0 for an observed zero, in row-major order of the internal matrix
+ * with columns ascending (what np.nonzero gives) -- becomes the context's eval set exactly as nbmf_set_eval would have
+ * installed it with those pairs, every and patience: nbmf_eval_loglik, the evaluations of nbmf_run, nbmf_get_eval and
+ * nbmf_get_best_factors work unchanged, and the sums are bit for bit those of the host route.  A plain eval set that was
+ * there is replaced.  The order of the list is fixed (row counts, a 64-bit exclusive prefix sum on the device, positions
+ * from ballots and population counts; integers only); *count (may be NULL) receives its length.  The lane masks, the
+ * observed counts (nbmf_get_n_obs drops by *count) and the per-row counts are made again as after an upload, so every
+ * later call sees the data as if it had been uploaded with the held-out entries masked.  Needs data on the byte-code
+ * path (NBMF_FLAG_BINARY_PATH; uploaded or generated), no factors: NBMF_ERR_STATE "hold-out needs binary data with a
+ * binary or no mask" otherwise, NBMF_ERR_STATE while a communicator is attached and while a hold-out is in place ("undo
+ * it first").  NBMF_ERR_ARG unless 0 <= lo < hi <= 1, every >= 1, patience >= 0; for a split that "holds out no entry" or
+ * "leaves no observed entry" -- the context is then exactly as it was, images, counts and any previous eval set: the
+ * entries are counted before anything changes --; and beyond the limits of nbmf_set_eval.
+ * nbmf_hold_out_undo: every listed entry is observed again with its value, the derived state is made again (data that was
+ * observed everywhere runs the two-state W sweep again), and the eval set is released.  NBMF_ERR_STATE without a hold-out.
+ * While a hold-out is in place nbmf_set_eval returns NBMF_ERR_STATE, with count == 0 too: the list is the only record of
+ * what was cleared.  A new nbmf_upload* / nbmf_generate* makes the context forget that its set came from a hold-out; the
+ * list stays, as a plain eval set does across an upload.
+ * nbmf_get_eval_pairs: the eval set the context holds, however it got there: *count (0 without one) and the first
+ * min(cap, *count) triples as int64 / int64 / uint8 in internal coordinates.  Any output pointer may be NULL. */
+int nbmf_hold_out(nbmf_ctx* ctx, uint64_t seed, int transposed, double lo, double hi, int every, int patience, int64_t* count);
+int nbmf_hold_out_undo(nbmf_ctx* ctx);
+int nbmf_get_eval_pairs(nbmf_ctx* ctx, int64_t cap, int64_t* count, int64_t* rows, int64_t* cols, uint8_t* x);
+
 /* Multi-GPU, one process (and one context) per GPU.  The internal matrix Y is split over the ranks along
  *   shard_axis 0: its ROWS    -> W[:, rows] is local, H is replicated; each iteration all-reduces the k x n
  *                 H-step products [P1 | P2 | loglik] (2*K*N+1 doubles) before the H-update;

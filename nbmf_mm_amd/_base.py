@@ -11,7 +11,7 @@ from sklearn.utils import check_array
 from . import _hip, _metrics
 from ._packed import PackedBits
 from ._solver import (device_predict, device_rank_of, device_score, device_score_samples, device_theta_bits, device_theta_hist,
-                      device_top_n, eval_pairs, nbmf_mm_restarts, nbmf_mm_solver, w_only_transform)
+                      device_top_n, eval_pairs, holdout_args, nbmf_mm_restarts, nbmf_mm_solver, w_only_transform)
 from ._utils import check_is_fitted
 
 # Accepted spellings of the two orientations: the exact strings of src/nbmf_mm/_base.py:127-137
@@ -113,7 +113,8 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         raise err
 
     # -- estimator API ---------------------------------------------------------------------------
-    def fit(self, X, y=None, mask=None, eval_mask=None, eval_every=10, patience=0, restore_best=True):
+    def fit(self, X, y=None, mask=None, eval_mask=None, eval_every=10, patience=0, restore_best=True, holdout=None,
+            holdout_seed=None):
         """Fit the factorisation to X (entries in [0, 1]); ``mask`` marks observed entries.
 
         ``eval_mask`` (dense bool / 0-1 or scipy-sparse, of X's shape): its nonzeros are HELD-OUT entries whose truth X
@@ -126,7 +127,17 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         ``restore_best`` (the default) ``W_`` and ``components_`` are the factors at ``best_iter_``; ``loss_curve_``,
         ``loss_`` and ``n_iter_`` stay the run's own -- they describe all ``n_iter_`` iterations that were made, not the
         restored factors.  ``n_init > 1`` with an eval set runs the restarts one after the other and keeps, as without
-        one, the restart with the lowest final training loss.  Not available with ``n_gpus > 1`` / ``devices``."""
+        one, the restart with the lowest final training loss.  Not available with ``n_gpus > 1`` / ``devices``.
+
+        ``holdout`` draws that eval set on the device instead: a fraction ``f`` in (0, 1), or a pair
+        ``(lo, hi)``, of the observed entries -- ``mask``, when given, is the pool the split draws from, so entries it leaves
+        out (a test set of the caller's own) are never held out -- chosen by a counter-based hash of ``(holdout_seed, entry)``;
+        :func:`holdout_mask` gives the same entries as a bool matrix.  They leave the fit and are evaluated exactly as
+        ``fit(X, mask=mask & ~held, eval_mask=held, ...)`` would, attribute for attribute and bit for bit, without a mask or
+        an index list crossing from the host.  ``holdout_seed`` defaults to ``random_state`` when that is an int, else to a
+        fresh draw; every restart of ``n_init > 1`` uses the same split.  Further attributes, only after a ``holdout`` fit:
+        ``holdout_seed_``, ``holdout_interval_`` and ``holdout_count_``.  Binary X with a binary (or no) mask only; not
+        together with ``eval_mask``, ``n_gpus > 1`` or ``devices``."""
         X = self._validated(X, keep_sparse=True)       # sparse V stays sparse up to the device (the solver decides)
         packed = isinstance(X, PackedBits)
         if isinstance(mask, PackedBits) and mask.shape != tuple(X.shape):
@@ -134,9 +145,19 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         if (packed or isinstance(mask, PackedBits)) and (int(self.n_gpus) != 1 or self.devices is not None):
             raise ValueError("PackedBits input is fitted on one GPU: it does not go with n_gpus > 1 or devices")
         # every error of the eval arguments is raised here, before any device work (the solver makes the pairs again)
-        eval_pairs(X, eval_mask, eval_every, patience, "beta-dir", self.n_gpus, self.devices)
+        split = holdout_args(holdout, holdout_seed, eval_mask, eval_every, patience, self.n_gpus, self.devices)
+        if split is None:
+            eval_pairs(X, eval_mask, eval_every, patience, "beta-dir", self.n_gpus, self.devices)
         ev = None if eval_mask is None else dict(eval_mask=eval_mask, eval_every=eval_every, patience=patience,
                                                  restore_best=bool(restore_best))
+        if split is not None:
+            seed = split[1]
+            if seed is None:                            # one split for every restart: random_state itself, else a fresh draw
+                rs = self.random_state
+                is_int = isinstance(rs, (int, np.integer)) and not isinstance(rs, (bool, np.bool_))
+                seed = _hip.sample_seed(int(rs) if is_int else None)
+            ev = dict(holdout=split[0], holdout_seed=seed, eval_every=eval_every, patience=patience,
+                      restore_best=bool(restore_best))
         if packed:                                      # (bits are binary: nothing to check; `sparse` skips the dense checks)
             return self._fit_validated(X, mask, sparse=True, ev=ev)
         if hasattr(X, "toarray"):
@@ -205,7 +226,8 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         self.loss_ = losses[-1] if losses else np.inf
         self.n_iter_ = n_iter
         self.reconstruction_err_ = losses[-1] if losses else np.inf
-        for name in ("eval_iters_", "eval_loglik_", "eval_perplexity_", "best_iter_", "stopped_early_"):
+        for name in ("eval_iters_", "eval_loglik_", "eval_perplexity_", "best_iter_", "stopped_early_", "holdout_seed_",
+                     "holdout_interval_", "holdout_count_"):
             if hasattr(self, name):
                 delattr(self, name)                                   # present only when an eval set was given
         if curve is not None:
@@ -214,6 +236,10 @@ class NBMFMM(BaseEstimator, TransformerMixin):
             self.eval_perplexity_ = np.exp(-self.eval_loglik_)
             self.best_iter_ = int(curve["best_iter"])
             self.stopped_early_ = bool(curve["stopped_early"])
+            if "seed" in curve:                                       # a holdout fit: what names the split
+                self.holdout_seed_ = int(curve["seed"])
+                self.holdout_interval_ = tuple(curve["interval"])
+                self.holdout_count_ = int(curve["count"])
         return self
 
     def fit_transform(self, X, y=None):
@@ -540,3 +566,15 @@ class NBMFMM(BaseEstimator, TransformerMixin):
 
 # alias kept for backwards compatibility (_base.py:269)
 NBMF = NBMFMM
+
+
+def holdout_mask(shape, seed, holdout, mask=None, rows=None, cols=None):
+    """The entries ``fit(X, mask=mask, holdout=holdout, holdout_seed=seed)`` holds out, as a bool matrix of X's ``shape``
+    (the same under both orientations): what to hand to ``roc_auc(X, mask=...)``, ``score_samples`` or ``rank_of``
+    afterwards, with ``seed = model.holdout_seed_`` and ``holdout = model.holdout_interval_``.  ``holdout`` is a fraction or
+    a pair as in ``fit`` (``_hip.holdout_interval``); ``mask`` the pool the split drew from (``None``: every entry).  Computed
+    on the host from the counter-based rule (``_hip.holdout_reference``).  Entries are hashed independently, so with index
+    arrays ``rows`` / ``cols`` -- the row slicing of ``hash_uniform`` -- the sub-matrix ``[rows][:, cols]`` costs only its own
+    size (``mask`` is then that sub-matrix's): a large shape is affordable one row block at a time."""
+    lo, hi = _hip.holdout_interval(holdout)
+    return _hip.holdout_reference(shape, seed, lo, hi, mask=mask, rows=rows, cols=cols)

@@ -42,7 +42,7 @@ SYMBOLS = [
     "nbmf_predict_at", "nbmf_predict_rows", "nbmf_top_n", "nbmf_score_rows", "nbmf_theta_hist",
     "nbmf_rank_rows", "nbmf_set_eval", "nbmf_eval_loglik", "nbmf_get_eval", "nbmf_get_best_factors",
     "nbmf_top_n_v", "nbmf_score_rows_v", "nbmf_theta_hist_v", "nbmf_rank_rows_v", "nbmf_selftest_unpack_bits",
-    "nbmf_theta_bits",
+    "nbmf_theta_bits", "nbmf_hold_out", "nbmf_hold_out_undo", "nbmf_get_eval_pairs",
 ]
 DATA_F64, DATA_U8, DATA_F32, DATA_BITS = 0, 1, 2, 3
 PREDICT_F64, PREDICT_U8 = 0, 1
@@ -201,6 +201,9 @@ def load():
     lib.nbmf_eval_loglik.argtypes = [c_void_p, dp]
     lib.nbmf_get_eval.argtypes = [c_void_p, c_int, POINTER(c_int), c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]
     lib.nbmf_get_best_factors.argtypes = [c_void_p, c_void_p, c_void_p]
+    lib.nbmf_hold_out.argtypes = [c_void_p, c_uint64, c_int, c_double, c_double, c_int, c_int, POINTER(c_int64)]
+    lib.nbmf_hold_out_undo.argtypes = [c_void_p]
+    lib.nbmf_get_eval_pairs.argtypes = [c_void_p, c_int64, POINTER(c_int64), c_void_p, c_void_p, c_void_p]
     for name in SYMBOLS:
         if name not in ("nbmf_last_error", "nbmf_source_hash"):
             getattr(lib, name).restype = c_int
@@ -600,6 +603,34 @@ class Context:
         _check(self._lib.nbmf_get_best_factors(self._h, W.ctypes.data_as(c_void_p), H.ctypes.data_as(c_void_p)))
         return W, H
 
+    def hold_out(self, seed, lo, hi, transposed=False, every=10, patience=0):
+        """Draw the held-out split on the device (``nbmf_hold_out``): every observed entry of the data the context holds
+        whose salted counter-based uniform lies in ``[lo, hi)`` -- :func:`holdout_reference` is the rule in NumPy, in the
+        USER's shape; ``transposed`` says that the user's matrix is the transpose of the internal one -- becomes
+        unobserved, and the list of them becomes the eval set, as :meth:`set_eval` with the pairs ``np.nonzero`` gives
+        for the internal matrix would have installed it.  Returns how many entries are held out.  Needs binary data on
+        the byte-code path; a split that holds out nothing, or everything observed, raises ``ValueError`` and changes
+        nothing.  :meth:`hold_out_undo` puts the entries back."""
+        count = c_int64(0)
+        _check(self._lib.nbmf_hold_out(self._h, sample_seed(seed), int(bool(transposed)), float(lo), float(hi), int(every),
+                                       int(patience), byref(count)))
+        return count.value
+
+    def hold_out_undo(self):
+        """Make the held-out entries observed again and release the eval set (``nbmf_hold_out_undo``): the context is as
+        it was before :meth:`hold_out`, with no new upload."""
+        _check(self._lib.nbmf_hold_out_undo(self._h))
+
+    def eval_pairs(self):
+        """The eval set the context holds (``nbmf_get_eval_pairs``), from :meth:`hold_out` or :meth:`set_eval`:
+        ``(rows, cols, x)`` as int64 / int64 / uint8 arrays in internal coordinates, empty without one."""
+        n = c_int64(0)
+        _check(self._lib.nbmf_get_eval_pairs(self._h, 0, byref(n), None, None, None))
+        rows, cols, x = np.zeros(n.value, np.int64), np.zeros(n.value, np.int64), np.zeros(n.value, np.uint8)
+        ptr = lambda a: a.ctypes.data_as(c_void_p)   # noqa: E731
+        _check(self._lib.nbmf_get_eval_pairs(self._h, n.value, byref(n), ptr(rows), ptr(cols), ptr(x)))
+        return rows, cols, x
+
     def _rows(self, row0, nrows):
         """``(row0, nrows)`` of a row-slab call as ints, ``nrows`` defaulting to the rest of the matrix: inside ``[0, m)``,
         or the library's own ``ValueError``."""
@@ -959,3 +990,47 @@ def sample_seed(random_state):
     if not 0 <= int(random_state) < 2 ** 64:
         raise ValueError(f"random_state must be in [0, 2**64) (got {int(random_state)})")
     return int(random_state)
+
+
+#: the salt of the hold-out uniform (``HO_SALT`` in nbmf_holdout_kernels.inc): a split is not the draw ``sample`` or ``generate`` made
+HOLDOUT_SALT = 0xA0761D6478BD642F
+
+
+def holdout_interval(holdout):
+    """The interval ``(lo, hi)`` of a ``holdout`` argument, checked without a device: a float ``f`` in (0, 1) means
+    ``(0.0, f)``, a pair ``(lo, hi)`` with ``0 <= lo < hi <= 1`` means itself.  Bools, NaN, ``lo >= hi`` and anything outside
+    [0, 1] raise ``ValueError``."""
+    def num(v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"holdout must be a fraction in (0, 1) or a pair (lo, hi) of numbers (got {holdout!r})")
+        v = float(v)
+        if not 0.0 <= v <= 1.0:   # (NaN fails both comparisons)
+            raise ValueError(f"holdout must lie in [0, 1] (got {holdout!r})")
+        return v
+    if isinstance(holdout, (tuple, list)):
+        if len(holdout) != 2:
+            raise ValueError(f"holdout must be a fraction in (0, 1) or a pair (lo, hi) (got {holdout!r})")
+        lo, hi = num(holdout[0]), num(holdout[1])
+    else:
+        lo, hi = 0.0, num(holdout)
+        if hi == 1.0:
+            raise ValueError(f"a holdout fraction must lie in (0, 1): {holdout!r} leaves nothing to fit")
+    if not lo < hi:
+        raise ValueError(f"holdout must be a fraction in (0, 1) or a pair 0 <= lo < hi <= 1 (got {holdout!r})")
+    return lo, hi
+
+
+def holdout_reference(shape, seed, lo, hi, mask=None, rows=None, cols=None):
+    """The entries ``Context.hold_out(seed, lo, hi)`` holds out, regenerated in NumPy: a bool matrix in the USER's shape
+    ``(U, V)`` -- under ``orientation="dir-beta"`` too: the counter of the entry at row u, column v is ``u * V + v`` whatever
+    the orientation -- true where the entry is observed (``mask`` nonzero; ``None``: everywhere) and
+    ``lo <= (splitmix64((seed * 0x100000001B3 + u * V + v) ^ 0xA0761D6478BD642F) >> 11) * 2**-53 < hi``.  With index arrays
+    ``rows`` / ``cols`` the sub-matrix ``[rows][:, cols]`` (``mask`` is then that sub-matrix's): entries are hashed
+    independently, so a slice costs only its own size."""
+    U, V = (int(d) for d in shape)
+    u = _hash_u01(U, V, sample_seed(seed), rows, cols, salt=HOLDOUT_SALT)
+    held = (u >= float(lo)) & (u < float(hi))
+    if mask is not None:
+        mask = np.asarray(mask)
+        held &= np.broadcast_to(mask, held.shape) != 0
+    return held

@@ -121,10 +121,38 @@ def eval_pairs(Y, eval_mask, eval_every=10, patience=0, orientation="beta-dir", 
             np.ascontiguousarray(v[order] != 0).view(np.uint8))
 
 
+def holdout_args(holdout, holdout_seed=None, eval_mask=None, eval_every=10, patience=0, n_gpus=1, devices=None):
+    """Every check of a fit's hold-out arguments -- none needs a device: ``((lo, hi), seed)`` with ``seed`` None where
+    the fit is to choose it, or None without a ``holdout``.  Raises ``ValueError`` for a bad interval
+    (``_hip.holdout_interval``), a ``holdout_seed`` that is no integer in ``[0, 2**64)``, a ``holdout_seed`` without a
+    ``holdout``, ``holdout`` together with ``eval_mask``, with ``n_gpus > 1`` or with ``devices``, ``eval_every < 1`` and
+    ``patience < 0``."""
+    if holdout is None:
+        if holdout_seed is not None:
+            raise ValueError("holdout_seed needs a holdout: it seeds the split")
+        return None
+    if eval_mask is not None:
+        raise ValueError("holdout draws the eval set on the device: it does not go with eval_mask")
+    interval = _hip.holdout_interval(holdout)
+    if holdout_seed is not None:
+        try:
+            holdout_seed = _hip.sample_seed(holdout_seed)
+        except ValueError:
+            raise ValueError(f"holdout_seed must be None or an integer in [0, 2**64) (got {holdout_seed!r})") from None
+    if int(n_gpus) != 1 or devices is not None:
+        raise ValueError("an eval set is evaluated on one GPU: holdout does not go with n_gpus > 1 or devices")
+    if isinstance(eval_every, (bool, np.bool_)) or not isinstance(eval_every, (int, np.integer)) or eval_every < 1:
+        raise ValueError(f"eval_every must be an integer >= 1 (got {eval_every!r})")
+    if isinstance(patience, (bool, np.bool_)) or not isinstance(patience, (int, np.integer)) or patience < 0:
+        raise ValueError(f"patience must be an integer >= 0 (got {patience!r})")
+    return interval, holdout_seed
+
+
 def nbmf_mm_solver(Y, n_components, max_iter=500, tol=1e-5, alpha=1.2, beta=1.2, W_init=None,
                    H_init=None, mask=None, random_state=None, verbose=0, orientation="beta-dir",
                    eps=1e-8, projection="normalize", device=0, n_gpus=1, devices=None, _ctx_hook=None,
-                   eval_mask=None, eval_every=10, patience=0, restore_best=True, _eval_out=None):
+                   eval_mask=None, eval_every=10, patience=0, restore_best=True, _eval_out=None, holdout=None,
+                   holdout_seed=None):
     """NBMF-MM on the GPU.  Returns ``(W (m,k), H (k,n), losses, 0.0, n_iter)``.
 
     Mirrors src/nbmf_mm/_solver.py:61-216 argument for argument; ``projection``, ``device`` and ``n_gpus`` / ``devices``
@@ -138,9 +166,18 @@ def nbmf_mm_solver(Y, n_components, max_iter=500, tol=1e-5, alpha=1.2, beta=1.2,
     returned are those of the best evaluation; ``losses`` and ``n_iter`` are the run's own either way.  The return value
     stays the reference's 5-tuple: the curve is left in the dict ``_eval_out`` (``iters``, ``logliks``, ``count``,
     ``best_iter``, ``stopped_early``), which is how the estimator gets it.
+
+    ``holdout`` (extension; see :func:`holdout_args`): the eval set is drawn on the device instead -- a fraction ``f`` of the
+    observed entries (those ``mask`` leaves in), or those whose uniform lies in a pair ``(lo, hi)``, by the counter-based
+    rule of ``_hip.holdout_reference`` with ``holdout_seed`` (default: ``random_state`` when that is an int, else a fresh
+    draw).  They leave the fit and are evaluated exactly as an ``eval_mask`` of the same entries would be, bit for bit; no
+    mask and no index list crosses from the host.  ``_eval_out`` also receives ``seed`` and ``interval``.  Binary data
+    only; not with ``eval_mask``, ``n_gpus > 1`` or ``devices``.
     """
-    pairs = eval_pairs(Y if hasattr(Y, "toarray") or eval_mask is None else np.asarray(Y), eval_mask, eval_every, patience,
-                       orientation, n_gpus, devices)
+    split = holdout_args(holdout, holdout_seed, eval_mask, eval_every, patience, n_gpus, devices)
+    pairs = None if split is not None else eval_pairs(
+        Y if hasattr(Y, "toarray") or eval_mask is None else np.asarray(Y), eval_mask, eval_every, patience, orientation, n_gpus,
+        devices)
     if (int(n_gpus) != 1 or devices is not None) and (isinstance(Y, PackedBits) or isinstance(mask, PackedBits)):
         raise ValueError("PackedBits input is fitted on one GPU: it does not go with n_gpus > 1 or devices")
     if int(n_gpus) != 1 or devices is not None:
@@ -161,6 +198,9 @@ def nbmf_mm_solver(Y, n_components, max_iter=500, tol=1e-5, alpha=1.2, beta=1.2,
         raise ValueError("max_iter must be >= 1")      # the reference dies with UnboundLocalError here (:215)
     if random_state is not None:
         np.random.seed(random_state)                   # GLOBAL legacy RNG, as :102-103
+    if split is not None and split[1] is None:         # the split's seed: random_state itself, else drawn before the init draws
+        is_int = isinstance(random_state, (int, np.integer)) and not isinstance(random_state, (bool, np.bool_))
+        split = (split[0], _hip.sample_seed(int(random_state) if is_int else None))
     # (sparse input: the reference densifies, :28-29,106-107; here upload_any keeps binary patterns sparse)
     if not hasattr(Y, "toarray"):
         Y = np.asarray(Y)
@@ -194,16 +234,25 @@ def nbmf_mm_solver(Y, n_components, max_iter=500, tol=1e-5, alpha=1.2, beta=1.2,
                     if it % 10 == 0:
                         print(f"Iter {it:4d}: Loss = {loss:.6f}", flush=True)
             ctx.set_progress(_report, every=10)
+        count = 0
         if pairs is not None:
             ctx.set_eval(*pairs, every=int(eval_every), patience=int(patience))
+            count = int(pairs[0].size)
+        elif split is not None:
+            try:
+                count = ctx.hold_out(split[1], *split[0], transposed=transposed, every=int(eval_every), patience=int(patience))
+            except _hip.NBMFHipError as e:             # (data on a real-valued storage path: the library's own words)
+                raise ValueError(str(e)) from None
+        evaluated = pairs is not None or split is not None
         losses, n_iter = ctx.run(int(max_iter), float(tol))
         stopped_early = False
-        if pairs is not None:
+        if evaluated:
             iters, logliks, best_iter, stopped_early = ctx.eval_curve()
             if _eval_out is not None:
-                _eval_out.update(iters=iters, logliks=logliks, count=int(pairs[0].size), best_iter=best_iter,
-                                 stopped_early=stopped_early)
-        Wk, Hk = ctx.best_factors() if pairs is not None and restore_best else ctx.get_factors()
+                _eval_out.update(iters=iters, logliks=logliks, count=count, best_iter=best_iter, stopped_early=stopped_early)
+                if split is not None:
+                    _eval_out.update(seed=split[1], interval=split[0])
+        Wk, Hk = ctx.best_factors() if evaluated and restore_best else ctx.get_factors()
 
     losses = [float(v) for v in losses]
     if verbose > 0 and stopped_early:

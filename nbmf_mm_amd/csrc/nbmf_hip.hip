@@ -326,6 +326,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 #include "nbmf_eval_kernels.inc"
 #include "nbmf_bits_kernels.inc"
 #include "nbmf_theta_bits_kernels.inc"
+#include "nbmf_holdout_kernels.inc"
 
 }  // namespace
 
@@ -450,6 +451,7 @@ struct nbmf_ctx {
     std::vector<int> iters;
     std::vector<double> logliks;
     int best_iter = 0, stopped_early = 0;
+    bool held_out = false;   // the set is a hold-out in place (nbmf_hold_out): its entries are unobserved in the images until the undo
   } eval;
   std::atomic<int> cancelled{0};   // nbmf_cancel (any thread): sticky; runs return NBMF_ERR_STATE at the next iteration boundary
   // timing
@@ -2688,7 +2690,7 @@ hipError_t launch_hist_panel(nbmf_ctx* c, const RowPanels& pl, long long p0, lon
 // ------------------------------------------------------------------------------------------
 extern "C" {
 
-int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows, nbmf_theta_hist, nbmf_rank_rows, nbmf_set_eval, nbmf_eval_loglik, nbmf_get_eval, nbmf_get_best_factors, the *_v forms and nbmf_selftest_unpack_bits, nbmf_theta_bits: compatible additions, which a caller detects by the symbol
+int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows, nbmf_theta_hist, nbmf_rank_rows, nbmf_set_eval, nbmf_eval_loglik, nbmf_get_eval, nbmf_get_best_factors, the *_v forms and nbmf_selftest_unpack_bits, nbmf_theta_bits, nbmf_hold_out, nbmf_hold_out_undo, nbmf_get_eval_pairs: compatible additions, which a caller detects by the symbol
 // The sources this binary was compiled from: first 12 hex digits of the SHA-256 over nbmf_hip.hip, the *.inc files (sorted
 // by name) and include/nbmf_hip.h, put in by the Makefile (tools/src_hash.sh prints the same for the tree).  A profile or a
 // bench line that quotes it can be tied to a commit; a library built by hand without the Makefile says "unstamped".
@@ -2925,6 +2927,7 @@ int nbmf_upload_v(nbmf_ctx* c, const void* xv, int x_kind, int64_t ldx, int tran
       *p = nullptr;
     }
     c->data_kind = -1;
+    c->eval.held_out = false;   // (new data: the list stays as a plain eval set)
     const size_t esz = binary ? 1 : 8;
     const size_t bytes = tiles * 256 * esz;
     HIPCHK(dmalloc(&c->dataA, bytes + PASS_SLACK));
@@ -3038,6 +3041,7 @@ int nbmf_generate_slice(nbmf_ctx* c, uint64_t seed, double density, double obser
     *p = nullptr;
   }
   c->data_kind = -1;
+  c->eval.held_out = false;   // (new data: the list stays as a plain eval set)
   const size_t tiles = (size_t)(c->mA / 16) * (c->nA / 16);
   HIPCHK(dmalloc(&c->dataA, tiles * 256 + PASS_SLACK));
   HIPCHK(dmalloc(&c->dataB, tiles * 256 + PASS_SLACK));
@@ -3092,6 +3096,7 @@ int nbmf_upload_csr(nbmf_ctx* c, const int64_t* indptr, const int32_t* indices, 
     *p = nullptr;
   }
   c->data_kind = -1;
+  c->eval.held_out = false;   // (new data: the list stays as a plain eval set)
   const long long RbA = c->mA / 16, RbB = c->nA / 16;
   const size_t tiles = (size_t)RbA * RbB;
   HIPCHK(dmalloc(&c->dataA, tiles * 256 + PASS_SLACK));
@@ -3558,6 +3563,8 @@ int nbmf_set_eval(nbmf_ctx* c, const int64_t* rows, const int64_t* cols, const u
   if (every < 1) return fail(NBMF_ERR_ARG, "every must be >= 1 (got %d)", every);
   if (patience < 0) return fail(NBMF_ERR_ARG, "patience must be >= 0 (got %d)", patience);
   if (is_sharded(c)) return fail(NBMF_ERR_STATE, "held-out evaluation runs on an unsharded context (nbmf_comm_detach first)");
+  if (c->eval.held_out)
+    return fail(NBMF_ERR_STATE, "the eval set is a hold-out in place, the only record of the entries it cleared: nbmf_hold_out_undo first");
   if (int rc = set_device(c)) return rc;
   auto& ev = c->eval;
   if (count == 0) {
@@ -3646,6 +3653,147 @@ int nbmf_get_best_factors(nbmf_ctx* c, double* W, double* H) {
     launch_get_factor(c, h, h ? c->eval.bestH : c->eval.bestW, c->stage);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, c->stage, sizeof(double) * (size_t)c->k * (h ? c->n : c->m), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return NBMF_OK;
+}
+
+// ---- the held-out split drawn on the device (nbmf_holdout_kernels.inc) ----------------------------------
+// Everything derived from the observed pattern, made again from the code images the way the tail of an upload makes it:
+// the lane-mask images (which also drops image B's pad marks), the pad marks where everything is observed again, the
+// observed counts and the per-row counts.  c->n_obs is the caller's.  Synchronises.
+static int rebuild_observed_state(nbmf_ctx* c) {
+  const long long n_tiles = (long long)(c->mA / 16) * (c->nA / 16);
+  for (int image = 0; image < 2; ++image) {
+    hipLaunchKernelGGL(mask_build_kernel, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, c->stream,
+                       (const uint32_t*)(image == 0 ? c->dataA : c->dataB), image == 0 ? c->bitsA : c->bitsB, n_tiles);
+    HIPCHK(hipGetLastError());
+  }
+  if (int rc = mark_pad_rows_b(c)) return rc;
+  c->n_obs_global = c->n_obs;
+  hipLaunchKernelGGL(rowcount_kernel, dim3((unsigned)((c->m + 255) / 256)), dim3(256), 0, c->stream, c->dataB, c->maskB,
+                     c->data_kind, (long long)(c->nA / 16), (long long)c->m, (long long)c->n, c->rowcnt);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return NBMF_OK;
+}
+
+int nbmf_hold_out(nbmf_ctx* c, uint64_t seed, int transposed, double lo, double hi, int every, int patience, int64_t* count) {
+  if (!c) return fail(NBMF_ERR_ARG, "null context");
+  if (!(lo >= 0.0 && lo < hi && hi <= 1.0)) return fail(NBMF_ERR_ARG, "the interval must satisfy 0 <= lo < hi <= 1 (got [%g, %g))", lo, hi);
+  if (every < 1) return fail(NBMF_ERR_ARG, "every must be >= 1 (got %d)", every);
+  if (patience < 0) return fail(NBMF_ERR_ARG, "patience must be >= 0 (got %d)", patience);
+  if (is_sharded(c)) return fail(NBMF_ERR_STATE, "held-out evaluation runs on an unsharded context (nbmf_comm_detach first)");
+  if (c->data_kind != DATA_BIN) return fail(NBMF_ERR_STATE, "hold-out needs binary data with a binary or no mask");
+  auto& ev = c->eval;
+  if (ev.held_out) return fail(NBMF_ERR_STATE, "a hold-out is already in place: undo it first (nbmf_hold_out_undo)");
+  if (c->m > 0x7fffffffLL || c->n > 0x7fffffffLL)
+    return fail(NBMF_ERR_ARG, "an eval set holds at most 2^35 pairs of a matrix with fewer than 2^31 rows and columns");
+  if (int rc = set_device(c)) return rc;
+  // (lo 2^53 and hi 2^53 are exact, and for the integer k of the uniform  lo <= k 2^-53 < hi  <=>  ceil(lo 2^53) <= k < ceil(hi 2^53))
+  HoldOutRule h{(unsigned long long)seed, (unsigned long long)ceil(lo * 9007199254740992.0), (unsigned long long)ceil(hi * 9007199254740992.0),
+                (long long)c->m, (long long)c->n, transposed ? 1 : 0};
+  const long long RbA = c->mA / 16, RbB = c->nA / 16, strips = (c->m + 15) / 16, tiles_e = (c->n + 15) / 16;
+  const long long nseg = (tiles_e + HO_SEG_TILES - 1) / HO_SEG_TILES, total = (long long)c->m * nseg;
+  const long long nb = (total + HO_SCAN_BLOCK - 1) / HO_SCAN_BLOCK;
+  const unsigned walk_grid = (unsigned)((strips * nseg + 3) / 4);
+  PredictStage scratch{c->stream, {}};
+  unsigned int* counts = nullptr;
+  unsigned long long *bsum = nullptr, *offs = nullptr;
+  HIPCHK(scratch.get(&counts, sizeof(unsigned int) * (size_t)total));
+  HIPCHK(scratch.get(&bsum, sizeof(unsigned long long) * (size_t)(nb + 1)));
+  // count first: a split that is refused has changed nothing
+  hipLaunchKernelGGL(holdout_count_kernel, dim3(walk_grid), dim3(256), 0, c->stream, (const uint32_t*)c->dataB, RbB, strips, nseg,
+                     tiles_e, h, counts);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(holdout_block_sum_kernel, dim3((unsigned)nb), dim3(256), 0, c->stream, (const unsigned int*)counts, total, bsum);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(holdout_scan_blocks_kernel, dim3(1), dim3(256), 0, c->stream, bsum, nb);
+  HIPCHK(hipGetLastError());
+  unsigned long long held = 0;
+  HIPCHK(hipMemcpyAsync(&held, bsum + nb, sizeof held, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (held == 0) return fail(NBMF_ERR_ARG, "the split [%g, %g) with seed %llu holds out no entry", lo, hi, (unsigned long long)seed);
+  if ((double)held >= c->n_obs)
+    return fail(NBMF_ERR_ARG, "the split [%g, %g) with seed %llu leaves no observed entry", lo, hi, (unsigned long long)seed);
+  if (held > (1ull << 35))
+    return fail(NBMF_ERR_ARG, "an eval set holds at most 2^35 pairs of a matrix with fewer than 2^31 rows and columns");
+  const size_t K = (size_t)c->k, cnt = (size_t)held;
+  const size_t nparts = (cnt + EV_PAIRS - 1) / EV_PAIRS;
+  PredictStage fresh{c->stream, {}};   // given back on every early return; emptied once the context owns the blocks
+  int *rows_d = nullptr, *cols_d = nullptr;
+  unsigned char* x_d = nullptr;
+  double *Wk = nullptr, *Hk = nullptr, *partials = nullptr;
+  HIPCHK(scratch.get(&offs, sizeof(unsigned long long) * (size_t)total));
+  HIPCHK(fresh.get(&rows_d, sizeof(int) * cnt));
+  HIPCHK(fresh.get(&cols_d, sizeof(int) * cnt));
+  HIPCHK(fresh.get(&x_d, cnt));
+  HIPCHK(fresh.get(&Wk, sizeof(double) * K * (size_t)c->m));
+  HIPCHK(fresh.get(&Hk, sizeof(double) * K * (size_t)c->n));
+  HIPCHK(fresh.get(&partials, sizeof(double) * nparts));
+  if (!ev.bestW) HIPCHK(dmalloc(&ev.bestW, sizeof(double) * (size_t)c->KP * c->mA));
+  if (!ev.bestH) HIPCHK(dmalloc(&ev.bestH, sizeof(double) * (size_t)c->KP * c->nA));
+  if (int rc = ensure_eval_slots(c, 1)) return rc;
+  // nothing below can be refused: the images change from here on
+  hipLaunchKernelGGL(holdout_scan_final_kernel, dim3((unsigned)nb), dim3(256), 0, c->stream, (const unsigned int*)counts, total,
+                     (const unsigned long long*)bsum, offs);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(holdout_scatter_kernel, dim3(walk_grid), dim3(256), 0, c->stream, (unsigned char*)c->dataA,
+                     (unsigned char*)c->dataB, RbA, RbB, strips, nseg, tiles_e, h, (const unsigned long long*)offs, rows_d, cols_d, x_d);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  eval_release(c);   // (the stream has just been drained)
+  fresh.blocks.clear();
+  ev.rows = rows_d;
+  ev.cols = cols_d;
+  ev.x = x_d;
+  ev.Wk = Wk;
+  ev.Hk = Hk;
+  ev.partials = partials;
+  ev.count = (int64_t)held;
+  ev.every = every;
+  ev.patience = patience;
+  ev.held_out = true;
+  c->n_obs -= (double)held;
+  if (int rc = rebuild_observed_state(c)) return rc;
+  if (count) *count = (int64_t)held;
+  return NBMF_OK;
+}
+
+int nbmf_hold_out_undo(nbmf_ctx* c) {
+  if (!c) return fail(NBMF_ERR_ARG, "null context");
+  auto& ev = c->eval;
+  if (!ev.held_out) return fail(NBMF_ERR_STATE, "no hold-out in place (nbmf_hold_out)");
+  if (int rc = set_device(c)) return rc;
+  hipLaunchKernelGGL(holdout_restore_kernel, dim3((unsigned)((ev.count + 255) / 256)), dim3(256), 0, c->stream,
+                     (unsigned char*)c->dataA, (unsigned char*)c->dataB, (long long)(c->mA / 16), (long long)(c->nA / 16),
+                     (const int*)ev.rows, (const int*)ev.cols, (const unsigned char*)ev.x, (long long)ev.count);
+  HIPCHK(hipGetLastError());
+  c->n_obs += (double)ev.count;
+  ev.held_out = false;
+  if (int rc = rebuild_observed_state(c)) return rc;
+  eval_release(c);   // (rebuild_observed_state has drained the stream)
+  return NBMF_OK;
+}
+
+int nbmf_get_eval_pairs(nbmf_ctx* c, int64_t cap, int64_t* count, int64_t* rows, int64_t* cols, uint8_t* x) {
+  if (!c) return fail(NBMF_ERR_ARG, "null context");
+  if (cap < 0) return fail(NBMF_ERR_ARG, "cap must be >= 0 (got %lld)", (long long)cap);
+  const auto& ev = c->eval;
+  if (count) *count = ev.count;
+  const size_t give = (size_t)std::min<int64_t>(cap, ev.count);
+  if (give == 0 || (!rows && !cols && !x)) return NBMF_OK;
+  if (int rc = set_device(c)) return rc;
+  std::vector<int> narrow(give);
+  for (const bool col : {false, true}) {
+    int64_t* dst = col ? cols : rows;
+    if (!dst) continue;
+    HIPCHK(hipMemcpyAsync(narrow.data(), col ? ev.cols : ev.rows, sizeof(int) * give, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (size_t t = 0; t < give; ++t) dst[t] = narrow[t];
+  }
+  if (x) {
+    HIPCHK(hipMemcpyAsync(x, ev.x, give, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   return NBMF_OK;

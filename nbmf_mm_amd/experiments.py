@@ -91,3 +91,56 @@ def perplexity_grid(Y, train_mask, eval_masks, n_components, alphas, betas, max_
     if group is not None and world > 1:
         rows = [r for part in group.all_gather(rows) for r in part]
     return sorted(rows, key=lambda r: (r["K"], r["alpha"], r["beta"]))
+
+
+def cross_validate(X, n_components, n_folds=5, mask=None, seed=0, alpha=1.2, beta=1.2, max_iter=500, tol=1e-5, eval_every=10,
+                   patience=0, random_state=12345, orientation="beta-dir", device=0):
+    """K-fold cross-validation of one model on ONE context and ONE upload of X: the folds are drawn, and put back, on the
+    device (``Context.hold_out`` / ``hold_out_undo``).  Fold f holds out the observed entries (those
+    ``mask`` leaves in; None: all) whose uniform under ``seed`` lies in ``[f / n_folds, (f + 1) / n_folds)`` -- one fold's
+    upper end and the next one's lower end are the same expression, so the folds partition the observed entries exactly
+    --, fits the rest from this module's init rule (``_init(m, n, k, random_state)`` in the internal layout, the same start
+    for every fold) and evaluates the held-out entries every ``eval_every`` iterations, ending early under ``patience``
+    as ``fit`` does.  X: binary, dense, scipy-sparse or ``PackedBits``.  One GPU; ``n_folds >= 2``.
+
+    Returns one dict per fold: ``fold``, ``count`` (held-out entries), ``n_iter``, ``loss`` (final training loss),
+    ``eval_iters``, ``eval_loglik`` (mean per held-out entry at each evaluation), ``perplexity`` (at the last evaluation),
+    ``best_iter``, ``best_perplexity`` and ``stopped_early``.  Fold f's numbers are those of
+    ``NBMF(...).fit(X, mask=mask, holdout=(f / n_folds, (f + 1) / n_folds), holdout_seed=seed, ...)`` from the same init."""
+    from ._solver import holdout_args, upload_any
+    if isinstance(n_folds, (bool, np.bool_)) or not isinstance(n_folds, (int, np.integer)) or n_folds < 2:
+        raise ValueError(f"n_folds must be an integer >= 2 (got {n_folds!r})")
+    if orientation not in ("beta-dir", "dir-beta"):
+        raise ValueError(f"Unknown orientation: {orientation}. Must be one of ['beta-dir', 'dir-beta']")
+    _, seed = holdout_args((0.0, 1.0 / n_folds), seed, None, eval_every, patience)
+    if not hasattr(X, "toarray"):
+        X = np.asarray(X)
+    m, n = X.shape
+    transposed = orientation == "dir-beta"
+    if transposed:
+        m, n = n, m
+    k = int(n_components)
+    W0, H0 = _init(m, n, k, random_state)
+    rows = []
+    with _hip.Context(m, n, k, device=device) as ctx:
+        ctx.set_hyper(alpha, beta, 1e-8, _hip.PROJ_NORMALIZE)
+        upload_any(ctx, X, mask, transposed=transposed)
+        for f in range(int(n_folds)):
+            try:
+                count = ctx.hold_out(seed, f / n_folds, (f + 1) / n_folds, transposed=transposed, every=int(eval_every),
+                                     patience=int(patience))
+            except _hip.NBMFHipError as e:
+                raise ValueError(str(e)) from None
+            try:
+                ctx.set_factors(W0, H0)
+                losses, n_iter = ctx.run(int(max_iter), float(tol))
+                iters, logliks, best_iter, stopped_early = ctx.eval_curve()
+            finally:
+                ctx.hold_out_undo()
+            mean_ll = np.asarray(logliks, dtype=np.float64) / count
+            perp = np.exp(-mean_ll)
+            rows.append({"fold": f, "count": int(count), "n_iter": int(n_iter), "loss": float(losses[-1]),
+                         "eval_iters": np.asarray(iters, dtype=np.int64), "eval_loglik": mean_ll, "perplexity": float(perp[-1]),
+                         "best_iter": int(best_iter), "best_perplexity": float(perp[list(iters).index(best_iter)]),
+                         "stopped_early": bool(stopped_early)})
+    return rows

@@ -32,7 +32,12 @@ that end in a synchronise (the library's predict calls do; NumPy's are synchrono
       as a ``PackedBits`` beside the thresholded bytes of (b) in the same process, the two differing in the bytes that cross
       PCIe (1/8) -- and ``sample`` -- one draw of Bernoulli(Theta) against the host route there was before it
       (predict_rows float64, ``default_rng().random(...) <``, ``np.packbits``).  The bits are checked for equality with
-      np.packbits of the byte slab, and with ``hash_uniform < `` the device's own float64 slab, before any time is taken.
+      np.packbits of the byte slab, and with ``hash_uniform < `` the device's own float64 slab, before any time is taken;
+  (j) the held-out split drawn on the device (``hold_out``): the data of (g) under its 90 % mask; ``Context.hold_out`` of 1 %
+      and of 10 % of the observed entries and ``Context.hold_out_undo``, median of five each, against the host route they
+      replace, timed once, stage by stage: ``rng.random(shape)``, the two comparisons, ``eval_pairs`` (np.nonzero and
+      np.lexsort), ``set_eval`` and the upload under the train mask.  The device's list is compared for equality with the
+      host's pairs of the same entries (``holdout_reference``) before any time is taken.
 
 The host legs are the comparison; the device path is never its own yardstick.  Before any time is taken the device and host
 results are compared at these sizes within tests/test_gpu_predict.py's bound, 2.1 K 2^-53 (|W| @ |H|) per entry; the
@@ -40,7 +45,8 @@ ranking is compared exactly with the host selection over the device's own slab (
 compared with the host's over the device's own slab within tests/test_gpu_score_samples.py's bound plus NumPy's own
 summation error; the class histograms and the ranks are compared for EQUALITY with NumPy's over the device's own slab.
 ``--legs`` picks the legs to time (default: the first four; ``theta_hist``, ``rank_of``, ``eval_curve`` and the ``*_bits`` legs are
-asked for by name, as are ``predict_bits`` and ``sample``; ``eval_curve`` alone skips the factors-only context and its agreement checks).
+asked for by name, as are ``predict_bits`` and ``sample``; ``eval_curve`` alone, or ``hold_out`` alone, skips the factors-only
+context and its agreement checks).
 Prints progress lines and, last, ONE JSON line.  Needs an MI355X: there is no CPU fallback."""
 import argparse
 import json
@@ -61,14 +67,14 @@ ap.add_argument("--rows", type=int, default=8192)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--legs", default="pairs,slabs,top_n,score_samples",
                 help="comma-separated: pairs, slabs, top_n, score_samples, theta_hist, rank_of, eval_curve, score_samples_bits, "
-                     "theta_hist_bits, top_n_bits, predict_bits, sample")
+                     "theta_hist_bits, top_n_bits, predict_bits, sample, hold_out")
 ap.add_argument("--device-only", action="store_true",
                 help="theta_hist, rank_of, predict_bits, sample: skip the timed host legs (for a kernel trace of the device legs)")
 args = ap.parse_args()
 legs = set(args.legs.split(","))
 BITS_LEGS = {"score_samples_bits", "theta_hist_bits", "top_n_bits"}
 DECISION_LEGS = {"predict_bits", "sample"}
-assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist", "rank_of", "eval_curve"} | BITS_LEGS | DECISION_LEGS, f"unknown leg in {args.legs}"
+assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist", "rank_of", "eval_curve", "hold_out"} | BITS_LEGS | DECISION_LEGS, f"unknown leg in {args.legs}"
 m, n, k, P, R = args.m, args.n, args.k, args.pairs, min(args.rows, args.m)
 
 
@@ -150,6 +156,95 @@ def eval_curve_leg():
             h[name] = t
     return h
 
+
+def hold_out_leg():
+    """(j): see the module docstring.  Its own data and context; ``--device-only`` skips the host route (for a kernel trace)."""
+    from nbmf_mm_amd._solver import eval_pairs
+    gh = np.random.default_rng(2029)
+    X = gh.random((m, n), dtype=np.float32) < 0.25
+    mask = gh.random((m, n), dtype=np.float32) < 0.90
+    image = ((m + 127) // 128 * 128) * ((n + 127) // 128 * 128)            # bytes of one code image
+    h = {"observed": int(mask.sum()), "image_bytes": image}
+    with _hip.Context(m, n, k) as ctx:
+        ctx.set_hyper(1.2, 1.2, 1e-8)
+        t0 = time.perf_counter()
+        ctx.upload(X, mask=mask)
+        h["upload_s"] = time.perf_counter() - t0
+        for name, f in (("1pct", 0.01), ("10pct", 0.10)):
+            t = {"fraction": f}
+            # equality first: the device's list against the host's pairs of the entries the rule names (row blocks: 8 bytes per entry)
+            count = ctx.hold_out(11, 0.0, f)
+            rows, cols, x = ctx.eval_pairs()
+            at = 0
+            for r0 in range(0, m, 4096):
+                r1 = min(m, r0 + 4096)
+                held = _hip.holdout_reference((m, n), 11, 0.0, f, mask=mask[r0:r1], rows=np.arange(r0, r1))
+                r, c = np.nonzero(held)
+                assert np.array_equal(rows[at:at + r.size], r + r0) and np.array_equal(cols[at:at + r.size], c), "list differs"
+                assert np.array_equal(x[at:at + r.size], X[r0:r1][r, c]), "truth differs"
+                at += r.size
+            assert at == count == rows.size and ctx.n_obs() == h["observed"] - count
+            ctx.hold_out_undo()
+            assert ctx.n_obs() == h["observed"]
+            del rows, cols, x
+            t["pairs"] = int(count)
+            outs, undos = [], []
+            for _ in range(args.reps + 1):                      # (the first round is the warm-up)
+                t0 = time.perf_counter()
+                ctx.hold_out(11, 0.0, f)
+                t1 = time.perf_counter()
+                ctx.hold_out_undo()
+                t2 = time.perf_counter()
+                outs.append(t1 - t0)
+                undos.append(t2 - t1)
+            t["hold_out_s"], t["hold_out_all_s"] = float(np.median(outs[1:])), [round(v, 6) for v in outs[1:]]
+            t["undo_s"], t["undo_all_s"] = float(np.median(undos[1:])), [round(v, 6) for v in undos[1:]]
+            # what the call moves: image B read by the count, the scatter and the row counts, both images read and a quarter
+            # of each written by the lane masks; 9 bytes listed and 2 bytes cleared per pair
+            t["hold_out_bytes"] = int(5.5 * image + 11 * count)
+            t["hold_out_GBps"] = t["hold_out_bytes"] / t["hold_out_s"] / 1e9
+            t["undo_bytes"] = int(3.5 * image + 11 * count)
+            t["undo_GBps"] = t["undo_bytes"] / t["undo_s"] / 1e9
+            say(f"{name}: hold_out {t['hold_out_s']:.6f} s ({t['hold_out_GBps']:.0f} GB/s), undo {t['undo_s']:.6f} s "
+                f"({t['undo_GBps']:.0f} GB/s), {count} pairs")
+            if not args.device_only:
+                host = {}
+                t0 = time.perf_counter()
+                u = np.random.default_rng(11).random((m, n))
+                host["rng_random_s"] = time.perf_counter() - t0
+                t0 = time.perf_counter()
+                held = mask & (u < f)
+                train = mask & ~held
+                host["comparisons_s"] = time.perf_counter() - t0
+                del u
+                t0 = time.perf_counter()
+                pairs = eval_pairs(X, held, 10, 0)
+                host["eval_pairs_s"] = time.perf_counter() - t0
+                del held
+                t0 = time.perf_counter()
+                ctx.upload(X, mask=train)
+                host["upload_train_mask_s"] = time.perf_counter() - t0
+                t0 = time.perf_counter()
+                ctx.set_eval(*pairs, every=10, patience=0)
+                host["set_eval_s"] = time.perf_counter() - t0
+                host["pairs"] = int(pairs[0].size)
+                host["total_s"] = sum(v for key, v in host.items() if key.endswith("_s"))
+                say(f"{name}: host route {host}")
+                ctx.set_eval(pairs[0][:0], pairs[1][:0], pairs[2][:0])
+                del pairs, train
+                ctx.upload(X, mask=mask)                        # the next split starts from the full pool again
+                t["host_route"] = host
+                t["speedup_vs_host_route"] = host["total_s"] / t["hold_out_s"]
+            h[name] = t
+    return h
+
+
+if legs == {"hold_out"}:
+    res = {"tool": "bench_predict", "library": _hip.source_hash(), "shape": [m, n, k], "reps": args.reps,
+           "hold_out_leg": hold_out_leg()}
+    print(json.dumps(res))
+    sys.exit(0)
+assert "hold_out" not in legs, "the hold_out leg runs alone: --legs hold_out"
 
 if legs == {"eval_curve"}:
     res = {"tool": "bench_predict", "library": _hip.source_hash(), "shape": [m, n, k], "reps": args.reps,
