@@ -347,6 +347,44 @@ int nbmf_theta_hist_v(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int bins,
                       const void* x, int x_kind, int64_t ldx, const void* mask, int mask_kind, int64_t ldmask,
                       int64_t* hist, int64_t* nan_count);
 
+/* The best entries of Theta over the whole row range [row0, row0 + nrows), as ONE list of (row, column) pairs ranked on the
+ * device: the global question nbmf_top_n (per row, at most NBMF_TOP_N_MAX slots) cannot answer.  theta[i, j] is bit for bit
+ * the entry nbmf_predict_rows(..., clip_theta, NBMF_PREDICT_F64, ...) returns.  Two kinds of request:
+ *   NBMF_PAIRS_THETA       score s = theta, best is LARGEST.  x is the exclude matrix (may be NULL: nothing is skipped): an
+ *                          entry is eligible unless its exclude byte or bit is nonzero.  Takes no mask.
+ *   NBMF_PAIRS_LIKELIHOOD  score s = theta where x != 0, else 1.0 - theta (one rounded subtraction): the probability the
+ *                          model gave to what was observed.  Best is SMALLEST.  x is the data; an entry is eligible where
+ *                          it is observed: mask nonzero, or mask_kind NBMF_MASK_NONE.
+ * In both kinds an entry whose score is NaN is never eligible, and columns >= n and rows outside the request do not exist.
+ * The result is the first `top` eligible entries in the order "score, best first, compared numerically (-0.0 equals +0.0),
+ * then ascending row, then ascending column": out_rows[s] (absolute row numbers), out_cols[s] and out_scores[s] (may be
+ * NULL; a score keeps its own bits, so a returned -0.0 is -0.0) for s < *out_count = min(top, eligible entries).  Slots at
+ * or beyond *out_count are not written; each array holds `top` entries.
+ * x_kind is NBMF_DATA_U8 (one byte per entry) or NBMF_DATA_BITS, mask_kind NBMF_MASK_NONE, NBMF_MASK_U8 or NBMF_MASK_BITS;
+ * operands are nrows x n with the leading-dimension rules of nbmf_theta_hist_v (bytes: >= n; packed: in bytes, >=
+ * ceil(n / 8)), nothing beyond column n - 1 is read, and packed operands are unpacked on the device into the staging the
+ * bytes are copied into: bits and bytes give identical results.  The operands go to the device once and stay there for
+ * the whole call (nrows x round_up(n, 4) bytes each, plus packed rows as they came, plus 24 bytes per candidate slot:
+ * top + max(65536, top / 8) of them, at least one row's worth; NBMF_PAIRS_SLACK in the environment sets the slack in
+ * entries, 0 forcing the selection through every digit and the tie pass -- the result is the same): a request that does not fit fails with NBMF_ERR_HIP and a message that says so --
+ * ask for fewer rows per call and merge.  No Theta panel is stored.
+ * The result depends on the factors, the operands and (row0, nrows, top) only -- not on how the work is blocked, on
+ * NBMF_HIST_COPIES (the copies of the digit counters, as nbmf_theta_hist), on NBMF_PAIRS_SLACK or on the order workgroups arrive in (integer
+ * adds only, no floating-point atomics; the candidates are sorted by (score, row, column) before they are returned) -- and
+ * the same call twice gives the same arrays.  So the call on a row range equals the merge of the calls on two ranges that
+ * partition it.
+ * NBMF_ERR_ARG, with nothing written, for top outside [1, NBMF_TOP_PAIRS_MAX], rows outside [0, m), an unknown kind, x_kind
+ * or mask_kind, a bad leading dimension, a mask given to NBMF_PAIRS_THETA, a NULL mask with mask_kind set, a NULL out_rows,
+ * out_cols or out_count, or a NULL x in the likelihood kind with nrows > 0.  nrows == 0 sets *out_count = 0 and reads
+ * nothing.  Same state rules and synchronisation as nbmf_predict_rows. */
+#define NBMF_TOP_PAIRS_MAX (1 << 22)
+#define NBMF_PAIRS_THETA 0
+#define NBMF_PAIRS_LIKELIHOOD 1
+int nbmf_top_pairs(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int64_t top, int clip_theta, int kind,
+                   const void* x, int x_kind, int64_t ldx,            /* THETA: the exclude matrix (may be NULL); LIKELIHOOD: the data */
+                   const void* mask, int mask_kind, int64_t ldmask,   /* LIKELIHOOD only; NBMF_MASK_NONE: all observed */
+                   int64_t* out_rows, int64_t* out_cols, double* out_scores, int64_t* out_count);
+
 /* Where given entries of Theta stand in the order nbmf_top_n ranks their row by: the position of held-out (row, column)
  * entries among all n columns, at any depth, with a few integers per entry leaving the device instead of the row.  The
  * TARGETS of row row0 + r are the columns indices[indptr[r] .. indptr[r + 1]) -- a CSR slice; indptr[0] may be greater than

@@ -11,7 +11,7 @@ from sklearn.utils import check_array
 from . import _hip, _metrics
 from ._packed import PackedBits
 from ._solver import (device_predict, device_rank_of, device_score, device_score_samples, device_theta_bits, device_theta_hist,
-                      device_top_n, eval_pairs, holdout_args, nbmf_mm_restarts, nbmf_mm_solver, w_only_transform)
+                      device_top_n, device_top_pairs, eval_pairs, holdout_args, nbmf_mm_restarts, nbmf_mm_solver, w_only_transform)
 from ._utils import check_is_fitted
 
 # Accepted spellings of the two orientations: the exact strings of src/nbmf_mm/_base.py:127-137
@@ -348,6 +348,34 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         n = _hip.top_n_count(n, name="n")
         exclude = self._entry_matrix(exclude, "exclude", W, H)
         return device_top_n(W, H, n, exclude=exclude, device=self.device)
+
+    # -- the global questions: the best entries of the whole matrix as (row, feature) pairs ----------------
+    def top_pairs(self, n=100, W=None, exclude=None):
+        """The ``n`` most probable entries of ``predict_proba(W)`` over the WHOLE matrix (``W`` defaulting to ``W_``) that
+        ``exclude`` does not mark, selected on the GPU: ``(rows, cols, scores)``, int64, int64 and float64, each
+        ``min(n, eligible entries)`` long, ordered by score descending, then row, then feature; ``scores`` holds exactly
+        those entries of ``predict_proba(W)``.  ``exclude`` as in :meth:`top_n` (dense bool / uint8 / 0-1 numeric,
+        :class:`PackedBits` or scipy-sparse; nonzero = never returned): ``exclude=X`` is the link-prediction query -- which
+        missing links are the most probable?  ``n`` is at most 2**22.  Unlike :meth:`top_n` this is one list, not one per
+        row, and it is not bounded by 256 slots a row; only ``n`` pairs leave the device and no Theta panel is ever stored
+        (DESIGN.md 4.15).  A sparse ``exclude`` goes up as packed bits, made row block by row block."""
+        W, H = self._prediction_factors(W)
+        n = _hip.top_pairs_count(n, name="n")
+        exclude = self._entry_matrix(exclude, "exclude", W, H)
+        return device_top_pairs(W, H, n, "theta", x=exclude, device=self.device)
+
+    def least_likely(self, X, mask=None, n=100, W=None):
+        """The ``n`` observed entries of the binary ``X`` to which the model gives the LOWEST probability, worst first,
+        selected on the GPU: ``(rows, cols, prob)`` with ``prob = predict_proba(W)`` where ``X`` is 1 and
+        ``1 - predict_proba(W)`` where it is 0, ordered by ``prob`` ascending, then row, then feature.  These are the
+        suspect cells of a data set: recorded presences the model does not believe and recorded absences it expects to be
+        presences.  ``X`` and ``mask`` as in :meth:`theta_histogram` (``X`` exactly 0 / 1: dense bool / uint8 / numeric,
+        :class:`PackedBits` or scipy-sparse; ``mask`` nonzero = observed, None: every entry); ``n`` is at most 2**22
+        (DESIGN.md 4.15)."""
+        W, H = self._prediction_factors(W)
+        n = _hip.top_pairs_count(n, name="n")
+        X, mask = self._scored_inputs(X, mask, W, H, exact=True)
+        return device_top_pairs(W, H, n, "likelihood", x=X, mask=mask, device=self.device)
 
     @staticmethod
     def _entry_matrix(a, name, W, H):

@@ -43,11 +43,14 @@ SYMBOLS = [
     "nbmf_rank_rows", "nbmf_set_eval", "nbmf_eval_loglik", "nbmf_get_eval", "nbmf_get_best_factors",
     "nbmf_top_n_v", "nbmf_score_rows_v", "nbmf_theta_hist_v", "nbmf_rank_rows_v", "nbmf_selftest_unpack_bits",
     "nbmf_theta_bits", "nbmf_hold_out", "nbmf_hold_out_undo", "nbmf_get_eval_pairs",
+    "nbmf_top_pairs",
 ]
 DATA_F64, DATA_U8, DATA_F32, DATA_BITS = 0, 1, 2, 3
 PREDICT_F64, PREDICT_U8 = 0, 1
 BITS_THRESHOLD, BITS_SAMPLE = 0, 1
 TOP_N_MAX = 256
+TOP_PAIRS_MAX = 1 << 22
+PAIRS_THETA, PAIRS_LIKELIHOOD = 0, 1
 HIST_MAX_BINS = 1024
 
 
@@ -191,6 +194,8 @@ def load():
     lib.nbmf_top_n_v.argtypes = [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64]
     lib.nbmf_score_rows_v.argtypes = [c_void_p, c_int64, c_int64, c_int, c_double, c_void_p, c_int, c_int64, c_void_p, c_int,
                                       c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.nbmf_top_pairs.argtypes = [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_int64, c_void_p, c_int, c_int64,
+                                   c_void_p, c_void_p, c_void_p, c_void_p]
     lib.nbmf_theta_hist_v.argtypes = [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int64, c_void_p, c_int, c_int64,
                                       c_void_p, c_void_p]
     lib.nbmf_rank_rows_v.argtypes = [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p,
@@ -285,6 +290,16 @@ def top_n_count(top, name="top"):
         raise ValueError(f"{name} must be an integer (got {top!r})")
     if not 1 <= int(top) <= TOP_N_MAX:
         raise ValueError(f"{name} must be in [1, {TOP_N_MAX}] (got {int(top)})")
+    return int(top)
+
+
+def top_pairs_count(top, name="top"):
+    """``top`` of ``top_pairs`` as an int, after the checks that need no device: an integer (not a bool) in
+    ``[1, TOP_PAIRS_MAX]``.  Raises ``ValueError`` otherwise."""
+    if isinstance(top, (bool, np.bool_)) or not isinstance(top, (int, np.integer)):
+        raise ValueError(f"{name} must be an integer (got {top!r})")
+    if not 1 <= int(top) <= TOP_PAIRS_MAX:
+        raise ValueError(f"{name} must be in [1, {TOP_PAIRS_MAX}] (got {int(top)})")
     return int(top)
 
 
@@ -758,6 +773,41 @@ class Context:
         _check(self._lib.nbmf_theta_hist_v(self._h, row0, nrows, bins, x.ctypes.data_as(c_void_p), x_kind, ldx, mptr, mkind, ldm,
                                            hist.ctypes.data_as(c_void_p), nan_count.ctypes.data_as(c_void_p)))
         return hist, nan_count
+
+    def top_pairs(self, top, kind="theta", x=None, mask=None, row0=0, nrows=None, clip_theta=True, return_scores=True):
+        """The ``top`` best entries of Theta over ALL of the rows ``[row0, row0 + nrows)``, selected on the device
+        (``nbmf_top_pairs``): ``(rows, cols, scores)``, int64, int64 and float64 (None without ``return_scores``), each
+        ``count = min(top, eligible entries)`` long; ``rows`` are absolute row numbers.  ``kind="theta"``: the largest
+        Theta first; ``x`` is an exclude matrix (nonzero = never return this entry) or None, and there is no mask.
+        ``kind="likelihood"``: ``x`` is the binary data, the score is ``Theta`` where ``x != 0`` and ``1 - Theta`` elsewhere
+        -- the probability the model gave to what was observed -- the smallest first, over the entries ``mask`` marks
+        (None: all).  The order is score, then row, then column (-0.0 ties +0.0); a NaN score is never returned; Theta is
+        bit for bit what :meth:`predict_rows` returns.  ``x`` and ``mask``: bool / uint8 of shape ``(nrows, n)`` (slices of
+        wider arrays are fine) or a :class:`PackedBits` of that shape (the same result).  Only ``count`` entries come back
+        from the device; no Theta panel is stored."""
+        top = top_pairs_count(top)
+        if kind not in ("theta", "likelihood"):
+            raise ValueError(f'kind must be "theta" or "likelihood" (got {kind!r})')
+        row0, nrows = self._rows(row0, nrows)
+        if kind == "theta" and mask is not None:
+            raise ValueError('kind="theta" takes an exclude matrix as x, not a mask')
+        if kind == "likelihood" and x is None:
+            raise ValueError('kind="likelihood" needs the data x')
+        xptr, xkind, ldx = None, DATA_U8, 0
+        if x is not None:
+            x, xkind, ldx = row_array(x, nrows, self.n, "x", BYTE_KINDS, packed=True)
+            xptr = x.ctypes.data_as(c_void_p)
+        mptr, mkind, ldm = self._mask_rows(mask, nrows)
+        rows = np.empty(top, dtype=np.int64)
+        cols = np.empty(top, dtype=np.int64)
+        scores = np.empty(top, dtype=np.float64) if return_scores else None
+        count = c_int64(0)
+        _check(self._lib.nbmf_top_pairs(self._h, row0, nrows, top, int(bool(clip_theta)),
+                                        PAIRS_THETA if kind == "theta" else PAIRS_LIKELIHOOD, xptr, xkind, ldx, mptr, mkind, ldm,
+                                        rows.ctypes.data_as(c_void_p), cols.ctypes.data_as(c_void_p),
+                                        None if scores is None else scores.ctypes.data_as(c_void_p), byref(count)))
+        cnt = int(count.value)
+        return rows[:cnt].copy(), cols[:cnt].copy(), None if scores is None else scores[:cnt].copy()
 
     def rank_of(self, indptr, indices, row0=0, nrows=None, exclude=None, clip_theta=True):
         """Where given columns stand in the order :meth:`top_n` ranks their row by, counted on the device

@@ -435,6 +435,46 @@ def device_top_n(W, H, top, exclude=None, device=0):
         return cols, scores
 
 
+def _one_call_operand(A, is_mask, what="X"):
+    """A binary ``(rows, features)`` operand of :func:`device_top_pairs` in a form that goes to the device in ONE call: a
+    dense bool / uint8 array with unit stride along a row and a :class:`PackedBits` as they are; anything else --
+    scipy-sparse, or dense of another dtype -- as a :class:`PackedBits` filled one row block of at most
+    ``TOP_N_EXCLUDE_BLOCK_BYTES`` dense bytes at a time, so the host never holds an m x n byte matrix of it.  Data
+    (``is_mask`` false) that is not exactly {0, 1} is a ``ValueError``; a mask or an exclude is ``!= 0``."""
+    if A is None or isinstance(A, PackedBits):
+        return A
+    if hasattr(A, "toarray"):
+        A = A.tocsr()
+    else:
+        A = np.asarray(A)
+        if A.dtype in (np.bool_, np.uint8):
+            return _row_block(A, 0, A.shape[0], is_mask)
+    m, n = A.shape
+    bits = np.zeros((m, (n + 7) // 8), dtype=np.uint8)
+    block = max(1, min(m, TOP_N_EXCLUDE_BLOCK_BYTES // max(n, 1)))
+    for r0 in range(0, m, block):
+        a = _row_block(A, r0, min(block, m - r0), is_mask)
+        if a.dtype == np.float64:
+            raise ValueError(f"{what} must be binary")
+        bits[r0:r0 + a.shape[0]] = np.packbits(a != 0, axis=1)
+    return PackedBits(bits, (m, n))
+
+
+def device_top_pairs(W, H, top, kind="theta", x=None, mask=None, device=0):
+    """The ``top`` best entries of Theta = clip(``W @ H``, 0, 1) over the whole matrix, selected on the GPU
+    (``Context.top_pairs``): ``(rows, cols, scores)``.  ``W``, ``H`` as in :func:`device_predict`; ``top`` already
+    validated (``_hip.top_pairs_count``).  ``kind="theta"``: the largest Theta, ``x`` an exclude matrix or None;
+    ``kind="likelihood"``: the observed entries of the binary data ``x`` that the model gives the lowest probability,
+    ``mask`` nonzero = observed.  ``x`` and ``mask``: shape ``(rows, features)``, dense or scipy-sparse or
+    :class:`PackedBits`.  The call keeps its operands on the device through all its passes, so they go up in one piece:
+    bool / uint8 arrays and packed bits as they are, anything else packed on the host block by block
+    (:func:`_one_call_operand`).  Factors only: no context holds the data."""
+    x = _one_call_operand(x, kind == "theta", "X")
+    mask = _one_call_operand(mask, True)
+    with _factors_only(W, H, device) as (ctx, m, n):
+        return ctx.top_pairs(top, kind, x=x, mask=mask, row0=0, nrows=m, clip_theta=True)
+
+
 def device_rank_of(W, H, targets_csr, exclude=None, device=0):
     """Where the target features of every row of ``W`` stand in the order :func:`device_top_n` ranks the row by, counted on
     the GPU (``Context.rank_of``): ``(rank, above, tied, scores, eligible)``, the first four indexed like the targets'

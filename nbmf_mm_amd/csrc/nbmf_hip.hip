@@ -322,6 +322,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 #include "nbmf_predict_kernels.inc"
 #include "nbmf_score_kernels.inc"
 #include "nbmf_hist_kernels.inc"
+#include "nbmf_pairs_kernels.inc"
 #include "nbmf_rank_kernels.inc"
 #include "nbmf_eval_kernels.inc"
 #include "nbmf_bits_kernels.inc"
@@ -2547,8 +2548,8 @@ int one_shot(nbmf_ctx* c, bool with_prior, int strict, int clip, bool collect_ti
 // (also the single-launch engine's end-of-run guard: small_guard)
 int loss_by_launches(nbmf_ctx* c, double* loss) { return one_shot(c, /*with_prior=*/true, 0, 0, /*collect_timing=*/true, loss); }
 
-// ---- shared by the seven entry points that read Theta back: nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows,
-// nbmf_theta_hist, nbmf_rank_rows, nbmf_theta_bits
+// ---- shared by the eight entry points that read Theta back: nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows,
+// nbmf_theta_hist, nbmf_rank_rows, nbmf_theta_bits, nbmf_top_pairs
 // (DESIGN.md 4.6).  Staging of one such call, from the pool: given back when the call returns, on every path, after the
 // stream has drained (a pooled block may be handed to the next caller at once).
 struct PredictStage {
@@ -2690,7 +2691,7 @@ hipError_t launch_hist_panel(nbmf_ctx* c, const RowPanels& pl, long long p0, lon
 // ------------------------------------------------------------------------------------------
 extern "C" {
 
-int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows, nbmf_theta_hist, nbmf_rank_rows, nbmf_set_eval, nbmf_eval_loglik, nbmf_get_eval, nbmf_get_best_factors, the *_v forms and nbmf_selftest_unpack_bits, nbmf_theta_bits, nbmf_hold_out, nbmf_hold_out_undo, nbmf_get_eval_pairs: compatible additions, which a caller detects by the symbol
+int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows, nbmf_theta_hist, nbmf_rank_rows, nbmf_set_eval, nbmf_eval_loglik, nbmf_get_eval, nbmf_get_best_factors, the *_v forms and nbmf_selftest_unpack_bits, nbmf_theta_bits, nbmf_hold_out, nbmf_hold_out_undo, nbmf_get_eval_pairs, nbmf_top_pairs: compatible additions, which a caller detects by the symbol
 // The sources this binary was compiled from: first 12 hex digits of the SHA-256 over nbmf_hip.hip, the *.inc files (sorted
 // by name) and include/nbmf_hip.h, put in by the Makefile (tools/src_hash.sh prints the same for the tree).  A profile or a
 // bench line that quotes it can be tied to a commit; a library built by hand without the Makefile says "unstamped".
@@ -4072,6 +4073,227 @@ int nbmf_theta_hist_v(nbmf_ctx* c, int64_t row0, int64_t nrows, int bins, const 
   HIPCHK(hipMemcpyAsync(nan, sum_d + slots, sizeof nan, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (nan_count) nan_count[0] = nan[0], nan_count[1] = nan[1];
+  return NBMF_OK;
+}
+
+// ---- the best entries of Theta over a row range, as (row, column) pairs (nbmf_pairs_kernels.inc) ----------
+// The operands go up once and stay staged for the whole call (no panels: every pass sees all rows).  Then a radix selection
+// on the 64-bit key, PAIRS_DIGIT_BITS at a time from the top, each pass a fused product-and-count whose PAIRS_BINS counters
+// come down to be scanned here; it ends as soon as the entries at or above the current bin's lower edge fit the candidate
+// buffer (top plus a slack), which one collecting pass then fills and this function sorts.  Only where the passes run to
+// the last digit and more entries equal the threshold key than the buffer holds does the tie pass run: the ties per row,
+// the boundary row from their prefix sum, the boundary column from that one row's ties, and a collecting pass that takes
+// exactly `top` entries.
+struct PairsCall {
+  nbmf_ctx* c;
+  dim3 grid;
+  long long row0, nrows, ldp;
+  int clip, kind;
+  const unsigned char *x_d, *m_d;
+};
+
+static unsigned long long host_pairs_key(double s, int kind) {   // pairs_key of an eligible entry, from its score
+  if (s != s) return 0ull;
+  unsigned long long k;
+  if (s == 0.0) {
+    k = 1ull << 63;
+  } else {
+    unsigned long long b;
+    memcpy(&b, &s, sizeof b);
+    k = (b >> 63) ? ~b : (b | (1ull << 63));
+  }
+  return kind == NBMF_PAIRS_LIKELIHOOD ? ~k : k;
+}
+
+// One collecting pass over the rows [p0, p0 + pn) of the request into the candidate arrays; *count = the entries taken.
+static int pairs_collect(const PairsCall& pc, long long p0, long long pn, unsigned long long lo, unsigned long long T, long long rs,
+                  long long cs, int row_only, unsigned long long cap, unsigned long long* counter_d, long long* rows_d,
+                  long long* cols_d, double* scores_d, unsigned long long* count) {
+  nbmf_ctx* c = pc.c;
+  HIPCHK(hipMemsetAsync(counter_d, 0, sizeof(unsigned long long), c->stream));
+  const dim3 grid((unsigned)RowPanels::blocks(p0, pn), pc.grid.y);
+  hipLaunchKernelGGL(pairs_collect_kernel, grid, dim3(PR_WAVES * 64), 0, c->stream, (const double*)c->Wn, (const double*)c->Hn, c->k,
+                     (long long)c->mA, (long long)c->nA, (long long)c->n, p0, pn, pc.row0, pc.ldp, pc.clip, pc.kind, pc.x_d, pc.m_d, lo,
+                     T, rs, cs, row_only, cap, counter_d, rows_d, cols_d, scores_d);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(count, counter_d, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (*count > cap) return fail(NBMF_ERR_HIP, "nbmf_top_pairs: %llu candidates for a buffer of %llu (internal error)", *count, cap);
+  return NBMF_OK;
+}
+
+int nbmf_top_pairs(nbmf_ctx* c, int64_t row0, int64_t nrows, int64_t top, int clip_theta, int kind, const void* x, int x_kind,
+                   int64_t ldx, const void* mask, int mask_kind, int64_t ldmask, int64_t* out_rows, int64_t* out_cols,
+                   double* out_scores, int64_t* out_count) {
+  if (int rc = predict_ready(c)) return rc;
+  if (top < 1 || top > NBMF_TOP_PAIRS_MAX)
+    return fail(NBMF_ERR_ARG, "top must be in [1, %d] (got %lld)", NBMF_TOP_PAIRS_MAX, (long long)top);
+  if (int rc = check_rows(c, row0, nrows)) return rc;
+  if (kind != NBMF_PAIRS_THETA && kind != NBMF_PAIRS_LIKELIHOOD) return fail(NBMF_ERR_ARG, "unknown kind %d", kind);
+  if (x_kind != NBMF_DATA_U8 && x_kind != NBMF_DATA_BITS) return fail(NBMF_ERR_ARG, "unknown x_kind %d", x_kind);
+  if (mask_kind != NBMF_MASK_NONE && mask_kind != NBMF_MASK_U8 && mask_kind != NBMF_MASK_BITS)
+    return fail(NBMF_ERR_ARG, "unknown mask_kind %d", mask_kind);
+  if (kind == NBMF_PAIRS_THETA && (mask_kind != NBMF_MASK_NONE || mask))
+    return fail(NBMF_ERR_ARG, "NBMF_PAIRS_THETA takes an exclude matrix, not a mask");
+  if (mask_kind != NBMF_MASK_NONE && !mask) return fail(NBMF_ERR_ARG, "mask_kind set but mask is NULL");
+  if (mask_kind == NBMF_MASK_NONE) mask = nullptr;
+  const bool xbits = x_kind == NBMF_DATA_BITS, mbits = mask_kind == NBMF_MASK_BITS;
+  if (x)
+    if (int rc = check_row_ld("ldx", ldx, xbits, c->n)) return rc;
+  if (mask)
+    if (int rc = check_row_ld("ldmask", ldmask, mbits, c->n)) return rc;
+  if (!out_rows || !out_cols || !out_count) return fail(NBMF_ERR_ARG, "null output");
+  if (kind == NBMF_PAIRS_LIKELIHOOD && nrows > 0 && !x) return fail(NBMF_ERR_ARG, "null data");
+  *out_count = 0;
+  if (nrows == 0) return NBMF_OK;
+  if (int rc = set_device(c)) return rc;
+
+  const long long n = c->n, ldp = panel_ld(c);
+  const long long col_groups = (c->nA + PR_WAVES * PR_STRIP - 1) / (PR_WAVES * PR_STRIP);
+  if (col_groups > 65535) return fail(NBMF_ERR_ARG, "n = %lld is beyond what nbmf_top_pairs launches", (long long)n);
+  // the candidate buffer: `top` and a slack that lets the selection end early, and never less than one row (the boundary row's ties)
+  // (NBMF_PAIRS_SLACK: the slack in entries, for tests -- 0 makes the selection run to the last digit and through the tie pass)
+  const unsigned long long slack = (unsigned long long)std::min<long long>(
+      1ll << 24, std::max<long long>(0, env_int("NBMF_PAIRS_SLACK", std::max<long long>(1ll << 16, (long long)top / 8))));
+  const unsigned long long cap = std::max<unsigned long long>((unsigned long long)top + slack, (unsigned long long)ldp);
+  const int copies = (int)std::min<long long>(1024, std::max<long long>(1, env_int("NBMF_HIST_COPIES", 64)));
+
+  PredictStage st{c->stream, {}};
+  unsigned char *x_d = nullptr, *m_d = nullptr, *xbits_d = nullptr, *mbits_d = nullptr;
+  unsigned long long *total_d = nullptr, *sum_d = nullptr, *counter_d = nullptr, *ties_d = nullptr;
+  long long *rows_d = nullptr, *cols_d = nullptr;
+  double* scores_d = nullptr;
+  const size_t panel_bytes = (size_t)nrows * ldp, bits_bytes = (size_t)nrows * packed_ld(n);
+  const size_t need_bytes = panel_bytes * ((x ? 1 : 0) + (mask ? 1 : 0)) + bits_bytes * ((x && xbits ? 1 : 0) + (mask && mbits ? 1 : 0)) +
+                            (size_t)cap * 24 + sizeof(unsigned long long) * PAIRS_BINS * ((size_t)copies + 1);
+  {
+    hipError_t e = hipSuccess;
+    if (x) e = st.get(&x_d, panel_bytes);
+    if (e == hipSuccess && mask) e = st.get(&m_d, panel_bytes);
+    if (e == hipSuccess && x && xbits) e = st.get(&xbits_d, bits_bytes);
+    if (e == hipSuccess && mask && mbits) e = st.get(&mbits_d, bits_bytes);
+    if (e == hipSuccess) e = st.get(&rows_d, sizeof(long long) * (size_t)cap);
+    if (e == hipSuccess) e = st.get(&cols_d, sizeof(long long) * (size_t)cap);
+    if (e == hipSuccess) e = st.get(&scores_d, sizeof(double) * (size_t)cap);
+    if (e == hipSuccess) e = st.get(&total_d, sizeof(unsigned long long) * PAIRS_BINS * (size_t)copies);
+    if (e == hipSuccess) e = st.get(&sum_d, sizeof(unsigned long long) * PAIRS_BINS);
+    if (e == hipSuccess) e = st.get(&counter_d, sizeof(unsigned long long));
+    if (e != hipSuccess)
+      return fail(NBMF_ERR_HIP,
+                  "nbmf_top_pairs keeps its operands on the device for the whole call and the %.1f MiB it needs for %lld rows do not "
+                  "fit (%s): ask for fewer rows per call and merge the results",
+                  (double)need_bytes / (1 << 20), (long long)nrows, hipGetErrorString(e));
+  }
+  if (x) HIPCHK(stage_rows_as_bytes(xbits_d, x, xbits, 1, ldx, n, nrows, x_d, ldp, c->stream));
+  if (mask) HIPCHK(stage_rows_as_bytes(mbits_d, mask, mbits, 1, ldmask, n, nrows, m_d, ldp, c->stream));
+
+  const PairsCall pc{c, dim3((unsigned)RowPanels::blocks(row0, nrows), (unsigned)col_groups), row0, nrows, ldp, clip_theta != 0 ? 1 : 0,
+                     kind, x_d, m_d};
+  const long long NO_ROW = 0x7fffffffffffffffLL;
+
+  // 1. select
+  unsigned long long prefix = 0, fixed = 0, need = (unsigned long long)top, n_gt = 0, in_bin = 0;
+  bool all = false, fits = false;
+  int passes = 0;
+  std::vector<unsigned long long> h(PAIRS_BINS);
+  for (int shift = 64 - PAIRS_DIGIT_BITS; !all && !fits && fixed != ~0ull; shift = std::max(0, shift - PAIRS_DIGIT_BITS)) {
+    const int bits = shift > 0 || passes == 0 ? PAIRS_DIGIT_BITS : 64 - passes * PAIRS_DIGIT_BITS;   // the last digit is what is left
+    const int bins = 1 << bits;
+    HIPCHK(hipMemsetAsync(total_d, 0, sizeof(unsigned long long) * PAIRS_BINS * (size_t)copies, c->stream));
+    hipLaunchKernelGGL(pairs_digit_kernel, pc.grid, dim3(PR_WAVES * 64), 0, c->stream, (const double*)c->Wn, (const double*)c->Hn,
+                       c->k, (long long)c->mA, (long long)c->nA, n, (long long)row0, (long long)nrows, (long long)row0, ldp, pc.clip,
+                       kind, (const unsigned char*)x_d, (const unsigned char*)m_d, prefix, fixed, shift, bins, copies, total_d);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(theta_hist_finish_kernel, dim3((unsigned)((PAIRS_BINS + 255) / 256)), dim3(256), 0, c->stream,
+                       (const unsigned long long*)total_d, copies, PAIRS_BINS, sum_d);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h.data(), sum_d, sizeof(unsigned long long) * (size_t)bins, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    ++passes;
+    unsigned long long above = 0;
+    int d = bins - 1;
+    for (; d >= 0 && above + h[d] < need; --d) above += h[d];   // from the best bin down
+    if (d < 0) {   // (first pass only: fewer eligible entries than `top`) -- every one of them is taken
+      all = true;
+      n_gt = above;
+      break;
+    }
+    n_gt += above;
+    need -= above;
+    in_bin = h[d];
+    prefix |= (unsigned long long)d << shift;
+    fixed |= (unsigned long long)(bins - 1) << shift;
+    fits = n_gt + in_bin <= cap;
+  }
+
+  // 2. collect
+  unsigned long long count = 0;
+  bool tie_pass = false;
+  if (all) {
+    if (n_gt > 0)
+      if (int rc = pairs_collect(pc, row0, nrows, 1ull, 1ull, NO_ROW, 0, 0, cap, counter_d, rows_d, cols_d, scores_d, &count)) return rc;
+  } else if (fits) {   // everything at or above the bin's lower edge
+    if (int rc = pairs_collect(pc, row0, nrows, prefix, prefix, NO_ROW, 0, 0, cap, counter_d, rows_d, cols_d, scores_d, &count)) return rc;
+  } else {   // prefix is the threshold key T in full, and more entries equal it than the buffer holds
+    tie_pass = true;
+    const unsigned long long T = prefix;
+    HIPCHK(st.get(&ties_d, sizeof(unsigned long long) * (size_t)nrows));
+    HIPCHK(hipMemsetAsync(ties_d, 0, sizeof(unsigned long long) * (size_t)nrows, c->stream));
+    hipLaunchKernelGGL(pairs_ties_kernel, pc.grid, dim3(PR_WAVES * 64), 0, c->stream, (const double*)c->Wn, (const double*)c->Hn, c->k,
+                       (long long)c->mA, (long long)c->nA, n, (long long)row0, (long long)nrows, (long long)row0, ldp, pc.clip, kind,
+                       (const unsigned char*)x_d, (const unsigned char*)m_d, T, ties_d);
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned long long> ties((size_t)nrows);
+    HIPCHK(hipMemcpyAsync(ties.data(), ties_d, sizeof(unsigned long long) * (size_t)nrows, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    long long r = 0;
+    unsigned long long before = 0;
+    for (; r < nrows && before + ties[(size_t)r] < need; ++r) before += ties[(size_t)r];
+    if (r >= nrows) return fail(NBMF_ERR_HIP, "nbmf_top_pairs: the tie counts do not reach the threshold (internal error)");
+    const long long rs = row0 + r;
+    const unsigned long long kth = need - before;   // the boundary row gives its first kth ties (>= 1)
+    if (int rc = pairs_collect(pc, rs, 1, T, T, rs, 0, 1, cap, counter_d, rows_d, cols_d, scores_d, &count)) return rc;
+    if (count < kth) return fail(NBMF_ERR_HIP, "nbmf_top_pairs: the boundary row has too few ties (internal error)");
+    std::vector<long long> tie_cols((size_t)count);
+    HIPCHK(hipMemcpy(tie_cols.data(), cols_d, sizeof(long long) * (size_t)count, hipMemcpyDeviceToHost));
+    std::nth_element(tie_cols.begin(), tie_cols.begin() + (size_t)(kth - 1), tie_cols.end());
+    const long long cs = tie_cols[(size_t)(kth - 1)];
+    if (int rc = pairs_collect(pc, row0, nrows, T, T, rs, cs, 0, cap, counter_d, rows_d, cols_d, scores_d, &count)) return rc;
+  }
+  if (env_set("NBMF_PAIRS_TRACE"))
+    fprintf(stderr, "nbmf_top_pairs: top %lld rows %lld digit_passes %d tie_pass %d collected %llu device_bytes %zu\n", (long long)top,
+            (long long)nrows, passes, tie_pass ? 1 : 0, count, need_bytes + (tie_pass ? sizeof(unsigned long long) * (size_t)nrows : 0));
+
+  // 3. sort: key descending, then row, then column -- the arrival order of the candidates does not survive this
+  struct Cand {
+    unsigned long long key;
+    long long row, col;
+    double score;
+  };
+  std::vector<Cand> cand((size_t)count);
+  if (count > 0) {
+    std::vector<long long> hr((size_t)count), hc((size_t)count);
+    std::vector<double> hs((size_t)count);
+    HIPCHK(hipMemcpy(hr.data(), rows_d, sizeof(long long) * (size_t)count, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hc.data(), cols_d, sizeof(long long) * (size_t)count, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hs.data(), scores_d, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost));
+    for (size_t q = 0; q < (size_t)count; ++q) cand[q] = Cand{host_pairs_key(hs[q], kind), hr[q], hc[q], hs[q]};
+  }
+  const auto first = [](const Cand& a, const Cand& b) {
+    return a.key != b.key ? a.key > b.key : a.row != b.row ? a.row < b.row : a.col < b.col;
+  };
+  const size_t keep = (size_t)std::min<unsigned long long>((unsigned long long)top, count);
+  if (keep < cand.size()) {
+    std::nth_element(cand.begin(), cand.begin() + keep, cand.end(), first);
+    cand.resize(keep);
+  }
+  std::sort(cand.begin(), cand.end(), first);
+  for (size_t q = 0; q < keep; ++q) {
+    out_rows[q] = cand[q].row;
+    out_cols[q] = cand[q].col;
+    if (out_scores) out_scores[q] = cand[q].score;
+  }
+  *out_count = (int64_t)keep;
   return NBMF_OK;
 }
 

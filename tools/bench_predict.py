@@ -37,7 +37,13 @@ that end in a synchronise (the library's predict calls do; NumPy's are synchrono
       and of 10 % of the observed entries and ``Context.hold_out_undo``, median of five each, against the host route they
       replace, timed once, stage by stage: ``rng.random(shape)``, the two comparisons, ``eval_pairs`` (np.nonzero and
       np.lexsort), ``set_eval`` and the upload under the train mask.  The device's list is compared for equality with the
-      host's pairs of the same entries (``holdout_reference``) before any time is taken.
+      host's pairs of the same entries (``holdout_reference``) before any time is taken;
+  (k) the best entries of the WHOLE matrix as (row, column) pairs (``top_pairs``; runs alone, all m rows): Context.top_pairs at
+      N = 100, 10^3, 10^5 and 2^22, plain and under a 10 %-dense exclude given as bytes and as bits, and the 10^4 least likely
+      observed entries of uint8 data under a 90 % mask -- against the host route there was before it, timed once: predict_rows
+      slab by slab, np.argpartition of every slab, a merge and a sort; for N <= 256 also top_n(N) on every row plus a host
+      merge.  The device result is compared for equality with the host selection over the device's own slabs before any
+      time is taken; the digit passes and the device memory of every request are the library's own report (NBMF_PAIRS_TRACE).
 
 The host legs are the comparison; the device path is never its own yardstick.  Before any time is taken the device and host
 results are compared at these sizes within tests/test_gpu_predict.py's bound, 2.1 K 2^-53 (|W| @ |H|) per entry; the
@@ -67,14 +73,14 @@ ap.add_argument("--rows", type=int, default=8192)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--legs", default="pairs,slabs,top_n,score_samples",
                 help="comma-separated: pairs, slabs, top_n, score_samples, theta_hist, rank_of, eval_curve, score_samples_bits, "
-                     "theta_hist_bits, top_n_bits, predict_bits, sample, hold_out")
+                     "theta_hist_bits, top_n_bits, predict_bits, sample, hold_out, top_pairs")
 ap.add_argument("--device-only", action="store_true",
                 help="theta_hist, rank_of, predict_bits, sample: skip the timed host legs (for a kernel trace of the device legs)")
 args = ap.parse_args()
 legs = set(args.legs.split(","))
 BITS_LEGS = {"score_samples_bits", "theta_hist_bits", "top_n_bits"}
 DECISION_LEGS = {"predict_bits", "sample"}
-assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist", "rank_of", "eval_curve", "hold_out"} | BITS_LEGS | DECISION_LEGS, f"unknown leg in {args.legs}"
+assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist", "rank_of", "eval_curve", "hold_out", "top_pairs"} | BITS_LEGS | DECISION_LEGS, f"unknown leg in {args.legs}"
 m, n, k, P, R = args.m, args.n, args.k, args.pairs, min(args.rows, args.m)
 
 
@@ -238,6 +244,120 @@ def hold_out_leg():
             h[name] = t
     return h
 
+
+def top_pairs_leg():
+    """(k): see the module docstring.  Its own factors-only context; ``--device-only`` skips the host routes (for a kernel trace)."""
+    import tempfile
+    from nbmf_mm_amd import PackedBits
+    gp = np.random.default_rng(2030)
+    W = gp.uniform(0.1, 0.9, (m, k))
+    W /= W.sum(1, keepdims=True)
+    H = gp.uniform(0.05, 0.95, (k, n))
+    excl = gp.random((m, n), dtype=np.float32) < 0.10
+    X = gp.random((m, n), dtype=np.float32) < 0.25
+    mask = gp.random((m, n), dtype=np.float32) < 0.90
+    pexcl = PackedBits.from_dense(excl)
+    slab = np.empty((R, n))
+
+    def traced(call):
+        """The call's result and the library's own report of it: digit passes, tie pass, candidates, device bytes."""
+        with tempfile.TemporaryFile() as f:
+            sys.stderr.flush()
+            keep = os.dup(2)
+            os.dup2(f.fileno(), 2)
+            os.environ["NBMF_PAIRS_TRACE"] = "1"
+            try:
+                out = call()
+            finally:
+                del os.environ["NBMF_PAIRS_TRACE"]
+                os.dup2(keep, 2)
+                os.close(keep)
+            f.seek(0)
+            words = f.read().decode().split()
+        rep = {key: int(words[words.index(key) + 1]) for key in ("digit_passes", "tie_pass", "collected", "device_bytes")}
+        return out, rep
+
+    def host_route(ctx, N, score_of, eligible, largest):
+        """predict_rows slab by slab, the N best of every slab by np.argpartition, a merge, and the sort by (score, row, col)."""
+        vals, rws, cls = [], [], []
+        for r0 in range(0, m, R):
+            nr = min(R, m - r0)
+            s = score_of(ctx.predict_rows(r0, nr, out=slab[:nr]), r0, nr)
+            if eligible is not None:
+                s = np.where(eligible[r0:r0 + nr], s, -np.inf if largest else np.inf)
+            flat = s.ravel()
+            keep = min(N, flat.size)
+            part = np.argpartition(flat, flat.size - keep)[flat.size - keep:] if largest else np.argpartition(flat, keep - 1)[:keep]
+            vals.append(flat[part])
+            rws.append(part // n + r0)
+            cls.append(part % n)
+        vals, rws, cls = np.concatenate(vals), np.concatenate(rws), np.concatenate(cls)
+        live = np.isfinite(vals)
+        vals, rws, cls = vals[live], rws[live], cls[live]
+        order = np.lexsort((cls, rws, -vals if largest else vals))[:N]
+        return rws[order], cls[order], vals[order]
+
+    def top_n_route(ctx, N):
+        """top_n(N) of every row on the device, then the merge on the host (N <= 256 only)."""
+        c, s = ctx.top_n(N, 0, m)
+        rws = np.repeat(np.arange(m), N)
+        c, s = c.ravel(), s.ravel()
+        part = np.argpartition(s, s.size - N)[s.size - N:]
+        order = part[np.lexsort((c[part], rws[part], -s[part]))]
+        return rws[order], c[order], s[order]
+
+    h = {"exclude_density": float(excl.mean()), "observed": float(mask.mean())}
+    with _hip.Context(m, n, k) as ctx:
+        ctx.set_factors(np.ascontiguousarray(W.T), H)
+        requests = []
+        for N in (100, 1000, 100000, 1 << 22):
+            requests.append((f"N{N}_plain", N, lambda N=N: ctx.top_pairs(N), None, None))
+            requests.append((f"N{N}_exclude_u8", N, lambda N=N: ctx.top_pairs(N, x=excl), ~excl, None))
+            requests.append((f"N{N}_exclude_bits", N, lambda N=N: ctx.top_pairs(N, x=pexcl), ~excl, f"N{N}_exclude_u8"))
+        requests.append(("least_likely_N10000", 10000, lambda: ctx.top_pairs(10000, kind="likelihood", x=X, mask=mask), mask, None))
+        for name, N, call, eligible, same_as in requests:
+            t = {"N": N}
+            likelihood = name.startswith("least_likely")
+            got, t["report"] = traced(call)
+            if same_as is not None:                             # the packed form: the host route is that of the byte form
+                t["host_route_s"] = h[same_as].get("host_route_s")
+                want = h[same_as].pop("_result")
+            elif not args.device_only:
+                score_of = (lambda th, r0, nr: np.where(X[r0:r0 + nr], th, 1.0 - th)) if likelihood else (lambda th, r0, nr: th)
+                t0 = time.perf_counter()
+                want = host_route(ctx, N, score_of, eligible, not likelihood)
+                t["host_route_s"] = time.perf_counter() - t0
+            else:
+                want = got
+            assert all(np.array_equal(a, b) for a, b in zip(got, want)), f"top_pairs {name} disagrees with the host selection"
+            if name.endswith("_exclude_u8"):
+                t["_result"] = want
+            t["device_s"], t["device_all_s"] = median_s(call)
+            say(f"top_pairs {name}: device {t['device_s']:.6f} s {t['report']}, host route {t.get('host_route_s')}")
+            if N <= _hip.TOP_N_MAX and name.endswith("_plain") and not args.device_only:
+                assert all(np.array_equal(a, b) for a, b in zip(got, top_n_route(ctx, N))), "top_n + merge disagrees"
+                t["top_n_then_merge_s"], t["top_n_then_merge_all_s"] = median_s(lambda: top_n_route(ctx, N))
+                say(f"top_pairs {name}: top_n({N}) of every row + host merge {t['top_n_then_merge_s']:.6f} s")
+            if t.get("host_route_s") is not None:
+                best = min(v for key, v in t.items() if key in ("host_route_s", "top_n_then_merge_s"))
+                t["speedup_vs_best_host_route"] = best / t["device_s"]
+                t["device_wins"] = bool(t["device_s"] < best)
+            h[name] = t
+        for t in h.values():
+            if isinstance(t, dict):
+                t.pop("_result", None)
+        wins = [t["device_wins"] for t in h.values() if isinstance(t, dict) and "device_wins" in t]
+        if wins:
+            h["no_device_leg_loses"] = all(wins)
+    return h
+
+
+if legs == {"top_pairs"}:
+    res = {"tool": "bench_predict", "library": _hip.source_hash(), "shape": [m, n, k], "reps": args.reps, "slab_rows": R,
+           "top_pairs_leg": top_pairs_leg()}
+    print(json.dumps(res))
+    sys.exit(0)
+assert "top_pairs" not in legs, "the top_pairs leg runs alone: --legs top_pairs"
 
 if legs == {"hold_out"}:
     res = {"tool": "bench_predict", "library": _hip.source_hash(), "shape": [m, n, k], "reps": args.reps,
