@@ -420,6 +420,40 @@ int nbmf_rank_rows_v(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int clip_theta,
                      int64_t* out_rank, int64_t* out_above, int64_t* out_tied, double* out_scores,
                      int64_t* out_eligible);
 
+/* Similarity within one side of the matrix: the factors read as an embedding.  The ITEMS of axis 0 are the m samples, whose
+ * vectors are the columns of W (k x m); the items of axis 1 are the n features, whose vectors are the columns of H (k x n).
+ * L is m or n accordingly, F the axis's factor and C the other one.  The score s(a, b) of items a and b, in float64:
+ *   NBMF_SIM_DOT      s = sum_k F[k, a] F[k, b]
+ *   NBMF_SIM_COSINE   s = u_a . u_b with u_a = F[:, a] / ||F[:, a]||_2; a zero vector has u = 0: its score with everything
+ *                     is 0, not NaN
+ *   NBMF_SIM_PROFILE  the cosine between the PREDICTED PROFILES of a and b -- the unclipped row of Theta of a sample, the
+ *                     column of Theta of a feature -- reduced to factor space: with G = C C^T (k x k),
+ *                     s = f_a^T G f_b / sqrt((f_a^T G f_a)(f_b^T G f_b)); an item with f^T G f = 0 scores 0 with everything.
+ *                     Two correlated components are not treated as unrelated by this one.
+ * `query` holds nq item indices in [0, L), in any order, repeats allowed; NULL means the items 0 .. nq - 1 (nq <= L then).
+ * nbmf_similarity writes s(query[t], b) for every item b to out[t * ldout + b] (ldout >= L; nothing beyond column L - 1 of a
+ * row is written).  An entry depends on its two items, the factors, axis and metric only -- not on the panels
+ * (NBMF_PREDICT_PANEL_ROWS, as nbmf_predict_rows; a panel row stages L doubles) or on the other queries -- and the same call
+ * twice gives the same bits (ordered sums, no floating-point atomics).  DOT and COSINE are bitwise symmetric:
+ * s(a, b) == s(b, a).  NBMF_ERR_ARG for an unknown axis or metric, nq < 0, nq > L with a NULL query, a query index outside
+ * [0, L) (the message names the lowest offending position; checked on the host before anything is launched), ldout < L,
+ * or a NULL out with nq > 0; nq == 0 touches nothing.  Same state rules and synchronisation as nbmf_predict_rows. */
+#define NBMF_SIM_DOT 0
+#define NBMF_SIM_COSINE 1
+#define NBMF_SIM_PROFILE 2
+int nbmf_similarity(nbmf_ctx* ctx, int axis, int metric, const int64_t* query, int64_t nq, double* out, int64_t ldout);
+/* The `top` items most similar to each query item, ranked on the device: nbmf_top_n's contract with "column" read as item
+ * and no clip.  For every query position t and slot s < top, out_idx[t * ldout + s] is the s-th item in the order "score
+ * descending (compared numerically), ties by ascending index" over the ELIGIBLE items of row t, and out_scores (may be
+ * NULL) its score, bit for bit the entry nbmf_similarity returns for the same (query, item).  An item is eligible unless
+ * its score is NaN or, with skip_self != 0, it IS query[t] -- by index: a different item with an identical vector stays
+ * eligible and ties by ascending index.  A row with fewer than `top` eligible items (top > L is allowed) ends in index
+ * -1 / score NaN; nothing outside slots [0, top) of an output row is written (ldout >= top, in elements).  A row's result
+ * depends on its query index, the factors, axis and metric only.  NBMF_ERR_ARG as nbmf_similarity, and for top outside
+ * [1, NBMF_TOP_N_MAX], ldout < top, or a NULL out_idx with nq > 0. */
+int nbmf_neighbors(nbmf_ctx* ctx, int axis, int metric, const int64_t* query, int64_t nq, int top, int skip_self,
+                   int64_t* out_idx, double* out_scores, int64_t ldout);
+
 /* Held-out entries kept on the device, and their Bernoulli log-likelihood summed there: the held-out curve of a fit
  * without the factors leaving the device, and early stopping on it.  `count` index pairs of the internal m x n matrix with
  * one byte of truth each (nonzero means x = 1), in any order, repeats allowed; 9 bytes per pair stay resident (rows and

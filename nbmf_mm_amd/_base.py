@@ -10,7 +10,7 @@ from sklearn.utils import check_array
 
 from . import _hip, _metrics
 from ._packed import PackedBits
-from ._solver import (device_predict, device_rank_of, device_score, device_score_samples, device_theta_bits, device_theta_hist,
+from ._solver import (device_neighbors, device_predict, device_rank_of, device_score, device_score_samples, device_theta_bits, device_theta_hist,
                       device_top_n, device_top_pairs, eval_pairs, holdout_args, nbmf_mm_restarts, nbmf_mm_solver, w_only_transform)
 from ._utils import check_is_fitted
 
@@ -348,6 +348,33 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         n = _hip.top_n_count(n, name="n")
         exclude = self._entry_matrix(exclude, "exclude", W, H)
         return device_top_n(W, H, n, exclude=exclude, device=self.device)
+
+    # -- similar items within one side of the matrix: the factors as an embedding ------------------------
+    def similar_features(self, n=10, features=None, metric="cosine"):
+        """The ``n`` features most similar to each of ``features`` (integer indices, any order, repeats allowed; None: every
+        feature), ranked on the GPU: ``(idx, scores)``, int64 and float64 of shape ``(len(features), n)``, as
+        :meth:`top_n` returns its columns.  A feature's vector is its column of ``components_``.  ``metric``: ``"dot"``;
+        ``"cosine"`` (a zero vector scores 0 with everything); or ``"profile"``, the cosine between the features'
+        predicted columns of ``W_ @ components_`` (unclipped), which does not count two correlated components as
+        unrelated.  Scores descending, ties by ascending index; the queried feature itself is left out by index, so a
+        duplicate of it is still returned.  A row with fewer than ``n`` other features ends in -1 / NaN.  ``n`` is at
+        most 256 (measured figures in profiles/neighbors_on_device.txt)."""
+        W, H = self._prediction_factors(None)
+        n = _hip.top_n_count(n, name="n")
+        metric = _hip.sim_metric(metric)
+        features, _ = _hip.item_query(features, H.shape[1], name="features")
+        return device_neighbors(W, H, n, axis=1, metric=metric, query=features, device=self.device)
+
+    def similar_samples(self, n=10, W=None, rows=None, metric="cosine"):
+        """The ``n`` rows of ``W`` (default ``W_``; ``transform(X_new)`` for unseen samples) most similar to each of its
+        ``rows`` (None: every row), ranked on the GPU: ``(idx, scores)`` of shape ``(len(rows), n)``.  A sample's vector is
+        its row of ``W``; ``metric`` as in :meth:`similar_features`, ``"profile"`` comparing the samples' predicted rows
+        ``W @ components_``.  The same order, tie rule and treatment of the queried row itself."""
+        W, H = self._prediction_factors(W)
+        n = _hip.top_n_count(n, name="n")
+        metric = _hip.sim_metric(metric)
+        rows, _ = _hip.item_query(rows, W.shape[0], name="rows")
+        return device_neighbors(W, H, n, axis=0, metric=metric, query=rows, device=self.device)
 
     # -- the global questions: the best entries of the whole matrix as (row, feature) pairs (DESIGN.md 4.15) ----------------
     def top_pairs(self, n=100, W=None, exclude=None):

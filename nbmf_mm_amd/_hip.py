@@ -43,7 +43,7 @@ SYMBOLS = [
     "nbmf_rank_rows", "nbmf_set_eval", "nbmf_eval_loglik", "nbmf_get_eval", "nbmf_get_best_factors",
     "nbmf_top_n_v", "nbmf_score_rows_v", "nbmf_theta_hist_v", "nbmf_rank_rows_v", "nbmf_selftest_unpack_bits",
     "nbmf_theta_bits", "nbmf_hold_out", "nbmf_hold_out_undo", "nbmf_get_eval_pairs",
-    "nbmf_top_pairs",
+    "nbmf_top_pairs", "nbmf_similarity", "nbmf_neighbors",
 ]
 DATA_F64, DATA_U8, DATA_F32, DATA_BITS = 0, 1, 2, 3
 PREDICT_F64, PREDICT_U8 = 0, 1
@@ -52,6 +52,9 @@ TOP_N_MAX = 256
 TOP_PAIRS_MAX = 1 << 22
 PAIRS_THETA, PAIRS_LIKELIHOOD = 0, 1
 HIST_MAX_BINS = 1024
+SIM_DOT, SIM_COSINE, SIM_PROFILE = 0, 1, 2
+#: the metric names of ``similarity`` / ``neighbors`` (``nbmf_similarity``)
+SIM_METRICS = {"dot": SIM_DOT, "cosine": SIM_COSINE, "profile": SIM_PROFILE}
 
 
 #: int fn(void* user, double* buf, int64 count) -- in-place sum over ranks on a host buffer
@@ -209,6 +212,8 @@ def load():
     lib.nbmf_hold_out.argtypes = [c_void_p, c_uint64, c_int, c_double, c_double, c_int, c_int, POINTER(c_int64)]
     lib.nbmf_hold_out_undo.argtypes = [c_void_p]
     lib.nbmf_get_eval_pairs.argtypes = [c_void_p, c_int64, POINTER(c_int64), c_void_p, c_void_p, c_void_p]
+    lib.nbmf_similarity.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64]
+    lib.nbmf_neighbors.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64]
     for name in SYMBOLS:
         if name not in ("nbmf_last_error", "nbmf_source_hash"):
             getattr(lib, name).restype = c_int
@@ -291,6 +296,41 @@ def top_n_count(top, name="top"):
     if not 1 <= int(top) <= TOP_N_MAX:
         raise ValueError(f"{name} must be in [1, {TOP_N_MAX}] (got {int(top)})")
     return int(top)
+
+
+def sim_axis(axis):
+    """``axis`` of ``similarity`` / ``neighbors`` as an int: 0 (samples) or 1 (features), not a bool.  ``ValueError``
+    otherwise."""
+    if isinstance(axis, (bool, np.bool_)) or not isinstance(axis, (int, np.integer)) or int(axis) not in (0, 1):
+        raise ValueError(f"axis must be 0 (samples) or 1 (features) (got {axis!r})")
+    return int(axis)
+
+
+def sim_metric(metric):
+    """``metric`` of ``similarity`` / ``neighbors`` as the library's code: one of the names in ``SIM_METRICS`` or its
+    code.  ``ValueError`` otherwise."""
+    if isinstance(metric, str) and metric in SIM_METRICS:
+        return SIM_METRICS[metric]
+    if not isinstance(metric, (bool, np.bool_)) and isinstance(metric, (int, np.integer)) and int(metric) in SIM_METRICS.values():
+        return int(metric)
+    raise ValueError(f"metric must be one of {sorted(SIM_METRICS)} (got {metric!r})")
+
+
+def item_query(query, L, name="query"):
+    """The ``query`` of ``similarity`` / ``neighbors`` as the library takes it (C-contiguous int64) and its length, after
+    the checks that need no device: integer-typed, 1-D, every index in ``[0, L)`` -- any order, repeats allowed.  None means
+    all ``L`` items: ``(None, L)``.  Raises ``ValueError`` otherwise, naming the lowest offending position."""
+    if query is None:
+        return None, int(L)
+    q = np.asarray(query)
+    if q.dtype == np.bool_ or not np.issubdtype(q.dtype, np.integer):
+        raise ValueError(f"{name} must be an integer array (got dtype {q.dtype})")
+    if q.ndim != 1:
+        raise ValueError(f"{name} must be 1-D (got shape {q.shape})")
+    bad = np.nonzero((q < 0) | (q >= L))[0]
+    if bad.size:
+        raise ValueError(f"{name} index at position {int(bad[0])} is outside [0, {int(L)})")
+    return np.ascontiguousarray(q, dtype=np.int64), int(q.size)
 
 
 def top_pairs_count(top, name="top"):
@@ -726,6 +766,45 @@ class Context:
                                       cols.ctypes.data_as(c_void_p), None if scores is None else scores.ctypes.data_as(c_void_p),
                                       top))
         return cols, scores
+
+    def similarity(self, axis=1, metric="cosine", query=None, out=None):
+        """The similarity of the ``query`` items to ALL items of one side of the matrix (``nbmf_similarity``): a float64
+        ``(len(query), L)`` slab.  ``axis`` 0: the items are the m samples (the columns of the internal W), 1: the n features
+        (the columns of H); L is m or n.  ``metric``: ``"dot"``, ``"cosine"`` (a zero vector scores 0 with everything, not
+        NaN) or ``"profile"`` -- the cosine between the items' predicted profiles, their unclipped rows (samples) or
+        columns (features) of Theta, which does not treat two correlated components as unrelated.  ``query``: integer
+        indices in ``[0, L)``, any order, repeats allowed; None: all items in order.  ``out``, if given, is written and
+        returned: float64 of shape ``(len(query), L)``, unit stride along a row, any row stride of at least L."""
+        axis, metric = sim_axis(axis), sim_metric(metric)
+        L = self.m if axis == 0 else self.n
+        query, nq = item_query(query, L)
+        if out is None:
+            out = np.empty((nq, L), dtype=np.float64)
+        elif not isinstance(out, np.ndarray):
+            raise ValueError(f"out must be a NumPy array: it is written in place (got {type(out).__name__})")
+        ld = row_array(out, nq, L, "out", (np.float64,))[2]
+        _check(self._lib.nbmf_similarity(self._h, axis, metric, None if query is None else query.ctypes.data_as(c_void_p), nq,
+                                         out.ctypes.data_as(c_void_p), ld))
+        return out
+
+    def neighbors(self, top, axis=1, metric="cosine", query=None, skip_self=True, return_scores=True):
+        """The ``top`` items most similar to each ``query`` item, ranked on the device (``nbmf_neighbors``):
+        ``(idx, scores)``, int64 and float64 of shape ``(len(query), top)`` (scores None without ``return_scores``).
+        ``axis``, ``metric`` and ``query`` as in :meth:`similarity`; slot s of a row holds the s-th item in the order "score
+        descending, ties by ascending index" and its score, bit for bit the entry :meth:`similarity` returns.  With
+        ``skip_self`` the query item itself is never returned -- by index: another item with the same vector is, and
+        ties by index.  A NaN score is never returned; a row with fewer than ``top`` items left ends in -1 / NaN."""
+        top = top_n_count(top)
+        axis, metric = sim_axis(axis), sim_metric(metric)
+        if not isinstance(skip_self, (bool, np.bool_)):
+            raise ValueError(f"skip_self must be a bool (got {skip_self!r})")
+        query, nq = item_query(query, self.m if axis == 0 else self.n)
+        idx = np.empty((nq, top), dtype=np.int64)
+        scores = np.empty((nq, top), dtype=np.float64) if return_scores else None
+        _check(self._lib.nbmf_neighbors(self._h, axis, metric, None if query is None else query.ctypes.data_as(c_void_p), nq, top,
+                                        int(bool(skip_self)), idx.ctypes.data_as(c_void_p),
+                                        None if scores is None else scores.ctypes.data_as(c_void_p), top))
+        return idx, scores
 
     def score_rows(self, x, mask=None, row0=0, nrows=None, clip_theta=True, eps=1e-8, rows=True, cols=False):
         """The Bernoulli log-likelihood of Theta against the data ``x`` of the rows ``[row0, row0 + nrows)``, summed per

@@ -435,6 +435,21 @@ def device_top_n(W, H, top, exclude=None, device=0):
         return cols, scores
 
 
+def device_neighbors(W, H, top, axis=1, metric="cosine", query=None, skip_self=True, device=0):
+    """The ``top`` items most similar to each ``query`` item within one side of the matrix, ranked on the GPU
+    (``Context.neighbors``): ``(idx, scores)``, both ``(len(query), top)``.  ``W`` (rows, k) and ``H`` (k, features) as in
+    :func:`device_predict`; ``axis`` 0 compares rows of ``W`` (samples), 1 columns of ``H`` (features); ``metric`` one of
+    ``"dot"``, ``"cosine"``, ``"profile"``; ``query`` None for all items.  Factors only: no data is uploaded."""
+    with _factors_only(W, H, device) as (ctx, m, n):
+        return ctx.neighbors(top, axis=axis, metric=metric, query=query, skip_self=skip_self)
+
+
+def device_similarity(W, H, axis=1, metric="cosine", query=None, device=0):
+    """The float64 ``(len(query), items)`` similarity slab behind :func:`device_neighbors` (``Context.similarity``)."""
+    with _factors_only(W, H, device) as (ctx, m, n):
+        return ctx.similarity(axis=axis, metric=metric, query=query)
+
+
 def _one_call_operand(A, is_mask, what="X"):
     """A binary ``(rows, features)`` operand of :func:`device_top_pairs` in a form that goes to the device in ONE call: a
     dense bool / uint8 array with unit stride along a row and a :class:`PackedBits` as they are; anything else --

@@ -328,6 +328,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 #include "nbmf_bits_kernels.inc"
 #include "nbmf_theta_bits_kernels.inc"
 #include "nbmf_holdout_kernels.inc"
+#include "nbmf_neighbors_kernels.inc"
 
 }  // namespace
 
@@ -2647,21 +2648,31 @@ struct RowPanels {
 };
 inline long long panel_ld(const nbmf_ctx* c) { return round_up(c->n, 4); }
 
-int plan_row_panels(nbmf_ctx* c, const char* who, int64_t row0, int64_t nrows, size_t row_bytes, bool align16, RowPanels* pl) {
-  const long long col_groups = (c->nA + PR_WAVES * PR_STRIP - 1) / (PR_WAVES * PR_STRIP);
-  if (col_groups > 65535) return fail(NBMF_ERR_ARG, "n = %lld is beyond what %s launches", (long long)c->n, who);
+// The plan for a product whose right operand has n real columns on an image nA long (a multiple of PR_STRIP): Theta's
+// (plan_row_panels) or the item-by-item product of nbmf_similarity / nbmf_neighbors, whose columns are the axis's items.
+int plan_panels(const char* who, long long n, long long nA, int64_t row0, int64_t nrows, size_t row_bytes, bool align16,
+                RowPanels* pl) {
+  const long long col_groups = (nA + PR_WAVES * PR_STRIP - 1) / (PR_WAVES * PR_STRIP);
+  if (col_groups > 65535) return fail(NBMF_ERR_ARG, "n = %lld is beyond what %s launches", n, who);
   const long long dflt = std::max<long long>(16, (long long)((256ull << 20) / row_bytes) / 16 * 16);
   const long long panel = std::max<long long>(1, env_int("NBMF_PREDICT_PANEL_ROWS", dflt));
-  *pl = RowPanels{panel_ld(c), col_groups, row0, row0 + nrows, align16 ? (long long)round_up(panel, 16) : panel, align16};
+  *pl = RowPanels{(long long)round_up(n, 4), col_groups, row0, row0 + nrows, align16 ? (long long)round_up(panel, 16) : panel, align16};
   return NBMF_OK;
 }
 
-// Rows [p0, p0 + pn) of Theta into the staging panel of leading dimension pl.ldp (nbmf_predict_rows, nbmf_top_n).
-hipError_t launch_theta_panel(nbmf_ctx* c, const RowPanels& pl, long long p0, long long pn, int out_kind, int clip, double threshold,
-                              void* panel_d) {
+int plan_row_panels(nbmf_ctx* c, const char* who, int64_t row0, int64_t nrows, size_t row_bytes, bool align16, RowPanels* pl) {
+  return plan_panels(who, (long long)c->n, (long long)c->nA, row0, nrows, row_bytes, align16, pl);
+}
+
+// Rows [p0, p0 + pn) of the product of two natural-layout operand images -- left[k * leftA + i], right[k * rightA + j], the
+// first c->k rows of each -- into the staging panel of leading dimension pl.ldp.  Theta is (c->Wn, c->mA, c->Hn, c->nA):
+// what nbmf_predict_rows, nbmf_top_n and nbmf_rank_rows pass; nbmf_similarity / nbmf_neighbors pass the gathered queries
+// and the prepared items.  leftA is a multiple of 16 that covers row p0 + pn - 1, rightA one of PR_STRIP.
+hipError_t launch_theta_panel(nbmf_ctx* c, const RowPanels& pl, const double* left, long long leftA, const double* right,
+                              long long rightA, long long p0, long long pn, int out_kind, int clip, double threshold, void* panel_d) {
   hipLaunchKernelGGL(out_kind == NBMF_PREDICT_U8 ? predict_rows_kernel<1> : predict_rows_kernel<0>, pl.grid(p0, pn),
-                     dim3(PR_WAVES * 64), 0, c->stream, (const double*)c->Wn, (const double*)c->Hn, c->k, (long long)c->mA,
-                     (long long)c->nA, p0, pn, pl.ldp, clip != 0 ? 1 : 0, threshold, panel_d);
+                     dim3(PR_WAVES * 64), 0, c->stream, left, right, c->k, leftA, rightA, p0, pn, pl.ldp, clip != 0 ? 1 : 0, threshold,
+                     panel_d);
   return hipGetLastError();
 }
 
@@ -2691,7 +2702,7 @@ hipError_t launch_hist_panel(nbmf_ctx* c, const RowPanels& pl, long long p0, lon
 // ------------------------------------------------------------------------------------------
 extern "C" {
 
-int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows, nbmf_theta_hist, nbmf_rank_rows, nbmf_set_eval, nbmf_eval_loglik, nbmf_get_eval, nbmf_get_best_factors, the *_v forms and nbmf_selftest_unpack_bits, nbmf_theta_bits, nbmf_hold_out, nbmf_hold_out_undo, nbmf_get_eval_pairs, nbmf_top_pairs: compatible additions, which a caller detects by the symbol
+int nbmf_abi_version(void) { return 4; }   // 2: NBMF_PEER_HANDLE_BYTES 128 -> 192, nbmf_generate_slice, nbmf_set_storage; 3: nbmf_upload_v (uint8 / bool data), nbmf_selftest_mfma_peak, nbmf_engine_stats; 4: nbmf_source_hash, nbmf_comm_info, nbmf_cancel, nbmf_variant_stats, nbmf_device_bus_id; still 4 with nbmf_predict_at, nbmf_predict_rows, nbmf_top_n, nbmf_score_rows, nbmf_theta_hist, nbmf_rank_rows, nbmf_set_eval, nbmf_eval_loglik, nbmf_get_eval, nbmf_get_best_factors, the *_v forms and nbmf_selftest_unpack_bits, nbmf_theta_bits, nbmf_hold_out, nbmf_hold_out_undo, nbmf_get_eval_pairs, nbmf_top_pairs, nbmf_similarity, nbmf_neighbors: compatible additions, which a caller detects by the symbol
 // The sources this binary was compiled from: first 12 hex digits of the SHA-256 over nbmf_hip.hip, the *.inc files (sorted
 // by name) and include/nbmf_hip.h, put in by the Makefile (tools/src_hash.sh prints the same for the tree).  A profile or a
 // bench line that quotes it can be tied to a commit; a library built by hand without the Makefile says "unstamped".
@@ -3818,7 +3829,7 @@ int nbmf_predict_rows(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, 
   HIPCHK(st.get(&panel_d, (size_t)pl.stage_rows() * pl.ldp * elt));
   for (long long p0 = row0, pn; p0 < pl.end; p0 += pn) {
     pn = pl.rows_at(p0);
-    HIPCHK(launch_theta_panel(c, pl, p0, pn, out_kind, clip_theta, threshold, panel_d));
+    HIPCHK(launch_theta_panel(c, pl, c->Wn, (long long)c->mA, c->Hn, (long long)c->nA, p0, pn, out_kind, clip_theta, threshold, panel_d));
     HIPCHK(copy_rows((char*)out + (size_t)(p0 - row0) * ldout * elt, ldout * elt, panel_d, pl.ldp * elt, c->n * elt, pn,
                      hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
@@ -3901,12 +3912,186 @@ int nbmf_top_n_v(nbmf_ctx* c, int64_t row0, int64_t nrows, int top, int clip_the
     const size_t done = (size_t)(p0 - row0);
     if (exclude)
       HIPCHK(stage_rows_as_bytes(exbits_d, (const char*)exclude + done * ldx, exbits, 1, ldx, n, pn, ex_d, n, c->stream));
-    HIPCHK(launch_theta_panel(c, pl, p0, pn, NBMF_PREDICT_F64, clip_theta, 0.0, panel_d));
-    hipLaunchKernelGGL(top_n_kernel, dim3((unsigned)pn), dim3(TN_THREADS), 0, c->stream, (const double*)panel_d, pl.ldp, n,
-                       (const unsigned char*)ex_d, n, top, cols_d, scores_d);
+    HIPCHK(launch_theta_panel(c, pl, c->Wn, (long long)c->mA, c->Hn, (long long)c->nA, p0, pn, NBMF_PREDICT_F64, clip_theta, 0.0,
+                              panel_d));
+    hipLaunchKernelGGL(top_n_kernel<0>, dim3((unsigned)pn), dim3(TN_THREADS), 0, c->stream, (const double*)panel_d, pl.ldp, n,
+                       (const unsigned char*)ex_d, n, top, cols_d, scores_d, (const long long*)nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(copy_rows(out_cols + done * ldout, pitch, cols_d, w64, w64, pn, hipMemcpyDeviceToHost, c->stream));
     if (out_scores) HIPCHK(copy_rows(out_scores + done * ldout, pitch, scores_d, w64, w64, pn, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
+  }
+  return NBMF_OK;
+}
+
+// ---- similar items: one side of the matrix against itself (nbmf_neighbors_kernels.inc) --------------------
+// Per call: the two operand images of the metric (DOT: the factor itself, twice; COSINE: the factor scaled by its items'
+// norms, twice; PROFILE: F d^(-1/2) and (G F) d^(-1/2) with G the other factor's Gram matrix and d = diag(F^T G F)), the
+// query items' columns of the left one gathered into a compact image, and then per panel of query rows the product kernel
+// of nbmf_predict_rows without a clip -- and for nbmf_neighbors the selection of nbmf_top_n with the row's own item
+// ineligible.  Both entry points run the same kernels on the same operands up to the panel: a neighbour's score is the
+// slab's entry by construction.
+}  // extern "C"
+namespace {
+
+struct SimCall {
+  long long L = 0, LA = 0, nqA = 0;   // items of the axis, their image length, the gathered image's length
+  const double* right = nullptr;      // [KP][LA]
+  double* left = nullptr;             // [KP][nqA]: the gathered queries
+  long long* query_d = nullptr;       // nq indices (the self column of each row)
+};
+
+int sim_check(nbmf_ctx* c, int axis, int metric, const int64_t* query, int64_t nq, long long* L_out) {
+  if (int rc = predict_ready(c)) return rc;
+  if (axis != 0 && axis != 1) return fail(NBMF_ERR_ARG, "axis must be 0 (samples) or 1 (features) (got %d)", axis);
+  if (metric != NBMF_SIM_DOT && metric != NBMF_SIM_COSINE && metric != NBMF_SIM_PROFILE)
+    return fail(NBMF_ERR_ARG, "unknown metric %d", metric);
+  const long long L = axis == 0 ? c->m : c->n;
+  if (nq < 0) return fail(NBMF_ERR_ARG, "nq must be >= 0 (got %lld)", (long long)nq);
+  if (!query && nq > L) return fail(NBMF_ERR_ARG, "nq = %lld without a query list is more than the %lld items", (long long)nq, L);
+  if (query)
+    for (int64_t t = 0; t < nq; ++t)
+      if (query[t] < 0 || query[t] >= L)
+        return fail(NBMF_ERR_ARG, "query index at position %lld is outside [0, %lld)", (long long)t, L);
+  *L_out = L;
+  return NBMF_OK;
+}
+
+// The operands of one call on the stream, from the call's staging.
+int sim_prepare(nbmf_ctx* c, int axis, int metric, const int64_t* query, int64_t nq, PredictStage& st, SimCall* sc) {
+  const int K = c->k, KP = c->KP;
+  const double* F = axis == 0 ? c->Wn : c->Hn;
+  const double* C = axis == 0 ? c->Hn : c->Wn;
+  const long long L = axis == 0 ? c->m : c->n, LA = axis == 0 ? c->mA : c->nA;
+  const long long lenC = axis == 0 ? c->n : c->m, lenCA = axis == 0 ? c->nA : c->mA;
+  const size_t img = sizeof(double) * (size_t)KP * LA;
+  const unsigned item_blocks = (unsigned)((L + NB_THREADS - 1) / NB_THREADS), image_blocks = (unsigned)(LA / NB_THREADS + (LA % NB_THREADS != 0));
+  const double *left = F, *right = F;
+  if (metric == NBMF_SIM_COSINE) {
+    double *d = nullptr, *U = nullptr;
+    HIPCHK(st.get(&d, sizeof(double) * (size_t)L));
+    HIPCHK(st.get(&U, img));
+    hipLaunchKernelGGL(item_dot_kernel, dim3(item_blocks), dim3(NB_THREADS), 0, c->stream, F, F, K, L, LA, d);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(item_scale_kernel, dim3(image_blocks, (unsigned)KP), dim3(NB_THREADS), 0, c->stream, F, (const double*)d, K, KP,
+                       L, LA, U);
+    HIPCHK(hipGetLastError());
+    left = right = U;
+  } else if (metric == NBMF_SIM_PROFILE) {
+    // the chunks of the Gram sum: at most NB_GRAM_BLOCKS of them, each a multiple of NB_GX items -- a function of lenC only
+    const long long want = std::min<long long>(NB_GRAM_BLOCKS, (lenC + 4 * NB_GX - 1) / (4 * NB_GX));
+    const long long chunk = round_up((lenC + want - 1) / want, NB_GX);
+    const int chunks = (int)((lenC + chunk - 1) / chunk);
+    const unsigned tiles = (unsigned)((K + NB_GT - 1) / NB_GT);
+    double *part = nullptr, *G = nullptr, *B = nullptr, *d = nullptr, *P = nullptr, *Q = nullptr;
+    HIPCHK(st.get(&part, sizeof(double) * (size_t)chunks * K * K));
+    HIPCHK(st.get(&G, sizeof(double) * (size_t)K * K));
+    HIPCHK(st.get(&B, sizeof(double) * (size_t)K * LA));
+    HIPCHK(st.get(&d, sizeof(double) * (size_t)L));
+    HIPCHK(st.get(&P, img));
+    HIPCHK(st.get(&Q, img));
+    hipLaunchKernelGGL(gram_partial_kernel, dim3((unsigned)chunks, tiles, tiles), dim3(NB_GT * NB_GT), 0, c->stream, C, K, lenC, lenCA,
+                       chunk, part);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(gram_sum_kernel, dim3((unsigned)((K * K + NB_THREADS - 1) / NB_THREADS)), dim3(NB_THREADS), 0, c->stream,
+                       (const double*)part, K, chunks, G);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(gram_apply_kernel, dim3(item_blocks, (unsigned)((K + NB_BT - 1) / NB_BT)), dim3(NB_THREADS), 0, c->stream,
+                       (const double*)G, F, K, L, LA, B);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(item_dot_kernel, dim3(item_blocks), dim3(NB_THREADS), 0, c->stream, F, (const double*)B, K, L, LA, d);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(item_scale_kernel, dim3(image_blocks, (unsigned)KP), dim3(NB_THREADS), 0, c->stream, F, (const double*)d, K, KP,
+                       L, LA, P);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(item_scale_kernel, dim3(image_blocks, (unsigned)KP), dim3(NB_THREADS), 0, c->stream, (const double*)B,
+                       (const double*)d, K, KP, L, LA, Q);
+    HIPCHK(hipGetLastError());
+    left = P;
+    right = Q;
+  }
+  sc->L = L;
+  sc->LA = LA;
+  sc->right = right;
+  sc->nqA = round_up(nq, 16);
+  HIPCHK(st.get(&sc->query_d, sizeof(long long) * (size_t)nq));
+  HIPCHK(st.get(&sc->left, sizeof(double) * (size_t)KP * sc->nqA));
+  std::vector<long long> iota;   // (a NULL query: the items 0 .. nq - 1)
+  if (!query) {
+    iota.resize((size_t)nq);
+    for (int64_t t = 0; t < nq; ++t) iota[(size_t)t] = t;
+  }
+  static_assert(sizeof(long long) == sizeof(int64_t), "the query list goes up as it is");
+  HIPCHK(hipMemcpyAsync(sc->query_d, query ? (const void*)query : (const void*)iota.data(), sizeof(long long) * (size_t)nq,
+                        hipMemcpyHostToDevice, c->stream));
+  if (!query) HIPCHK(hipStreamSynchronize(c->stream));   // (iota leaves scope with this function)
+  hipLaunchKernelGGL(gather_items_kernel, dim3((unsigned)((sc->nqA + NB_THREADS - 1) / NB_THREADS), (unsigned)KP), dim3(NB_THREADS), 0,
+                     c->stream, left, LA, (const long long*)sc->query_d, K, (long long)nq, sc->nqA, sc->left);
+  HIPCHK(hipGetLastError());
+  return NBMF_OK;
+}
+
+}  // namespace
+extern "C" {
+
+int nbmf_similarity(nbmf_ctx* c, int axis, int metric, const int64_t* query, int64_t nq, double* out, int64_t ldout) {
+  long long L = 0;
+  if (int rc = sim_check(c, axis, metric, query, nq, &L)) return rc;
+  if (ldout < L) return fail(NBMF_ERR_ARG, "ldout %lld is less than the %lld items", (long long)ldout, L);
+  if (nq == 0) return NBMF_OK;
+  if (!out) return fail(NBMF_ERR_ARG, "null output");
+  if (int rc = set_device(c)) return rc;
+  RowPanels pl;
+  if (int rc = plan_panels("nbmf_similarity", L, axis == 0 ? c->mA : c->nA, 0, nq, (size_t)round_up(L, 4) * sizeof(double), false, &pl))
+    return rc;
+  PredictStage st{c->stream, {}};
+  SimCall sc;
+  if (int rc = sim_prepare(c, axis, metric, query, nq, st, &sc)) return rc;
+  double* panel_d = nullptr;
+  HIPCHK(st.get(&panel_d, sizeof(double) * (size_t)pl.stage_rows() * pl.ldp));
+  for (long long p0 = 0, pn; p0 < pl.end; p0 += pn) {
+    pn = pl.rows_at(p0);
+    HIPCHK(launch_theta_panel(c, pl, sc.left, sc.nqA, sc.right, sc.LA, p0, pn, NBMF_PREDICT_F64, 0, 0.0, panel_d));
+    HIPCHK(copy_rows(out + (size_t)p0 * ldout, sizeof(double) * (size_t)ldout, panel_d, sizeof(double) * (size_t)pl.ldp,
+                     sizeof(double) * (size_t)L, pn, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
+  }
+  return NBMF_OK;
+}
+
+int nbmf_neighbors(nbmf_ctx* c, int axis, int metric, const int64_t* query, int64_t nq, int top, int skip_self, int64_t* out_idx,
+                   double* out_scores, int64_t ldout) {
+  long long L = 0;
+  if (int rc = sim_check(c, axis, metric, query, nq, &L)) return rc;
+  if (top < 1 || top > NBMF_TOP_N_MAX) return fail(NBMF_ERR_ARG, "top must be in [1, %d] (got %d)", NBMF_TOP_N_MAX, top);
+  if (ldout < top) return fail(NBMF_ERR_ARG, "ldout %lld is less than top = %d", (long long)ldout, top);
+  if (nq == 0) return NBMF_OK;
+  if (!out_idx) return fail(NBMF_ERR_ARG, "null output");
+  if (int rc = set_device(c)) return rc;
+  RowPanels pl;
+  if (int rc = plan_panels("nbmf_neighbors", L, axis == 0 ? c->mA : c->nA, 0, nq, (size_t)round_up(L, 4) * sizeof(double), false, &pl))
+    return rc;
+  PredictStage st{c->stream, {}};
+  SimCall sc;
+  if (int rc = sim_prepare(c, axis, metric, query, nq, st, &sc)) return rc;
+  const size_t rows = (size_t)pl.stage_rows(), w64 = sizeof(int64_t) * (size_t)top, pitch = sizeof(int64_t) * (size_t)ldout;
+  double *panel_d = nullptr, *scores_d = nullptr;
+  long long* idx_d = nullptr;
+  HIPCHK(st.get(&panel_d, sizeof(double) * rows * pl.ldp));
+  HIPCHK(st.get(&idx_d, rows * w64));
+  if (out_scores) HIPCHK(st.get(&scores_d, rows * w64));
+  for (long long p0 = 0, pn; p0 < pl.end; p0 += pn) {
+    pn = pl.rows_at(p0);
+    HIPCHK(launch_theta_panel(c, pl, sc.left, sc.nqA, sc.right, sc.LA, p0, pn, NBMF_PREDICT_F64, 0, 0.0, panel_d));
+    if (skip_self)
+      hipLaunchKernelGGL(top_n_kernel<1>, dim3((unsigned)pn), dim3(TN_THREADS), 0, c->stream, (const double*)panel_d, pl.ldp, L,
+                         (const unsigned char*)nullptr, 0LL, top, idx_d, scores_d, (const long long*)(sc.query_d + p0));
+    else
+      hipLaunchKernelGGL(top_n_kernel<0>, dim3((unsigned)pn), dim3(TN_THREADS), 0, c->stream, (const double*)panel_d, pl.ldp, L,
+                         (const unsigned char*)nullptr, 0LL, top, idx_d, scores_d, (const long long*)nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_rows(out_idx + (size_t)p0 * ldout, pitch, idx_d, w64, w64, pn, hipMemcpyDeviceToHost, c->stream));
+    if (out_scores) HIPCHK(copy_rows(out_scores + (size_t)p0 * ldout, pitch, scores_d, w64, w64, pn, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
   }
   return NBMF_OK;
@@ -4367,7 +4552,8 @@ int nbmf_rank_rows_v(nbmf_ctx* c, int64_t row0, int64_t nrows, int clip_theta, c
       HIPCHK(stage_rows_as_bytes(exbits_d, (const char*)exclude + done * ldx, exbits, 1, ldx, n, pn, ex_d, n, c->stream));
     HIPCHK(hipMemcpyAsync(indptr_d, indptr + done, sizeof(long long) * (size_t)(pn + 1), hipMemcpyHostToDevice, c->stream));
     if (cnt) HIPCHK(hipMemcpyAsync(indices_d, indices + base, sizeof(int) * cnt, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(launch_theta_panel(c, pl, p0, pn, NBMF_PREDICT_F64, clip_theta, 0.0, panel_d));
+    HIPCHK(launch_theta_panel(c, pl, c->Wn, (long long)c->mA, c->Hn, (long long)c->nA, p0, pn, NBMF_PREDICT_F64, clip_theta, 0.0,
+                              panel_d));
     hipLaunchKernelGGL(rank_rows_kernel, dim3((unsigned)pn), dim3(RK_THREADS), 0, c->stream, (const double*)panel_d, pl.ldp, n,
                        (const unsigned char*)ex_d, n, (const long long*)indptr_d, (const int*)indices_d, base, rank_d, above_d,
                        tied_d, scores_d, elig_d);

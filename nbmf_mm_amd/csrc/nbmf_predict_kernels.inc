@@ -179,9 +179,15 @@ __device__ __forceinline__ unsigned long long top_n_key(double v, bool skip) {
 //      order: the tie rule.  Entry lists in LDS: keys above T in slots [0, n_gt), the ties in [n_gt, n_gt + n_eq).
 //   3. sort: a bitonic network over the smallest power of two >= top, key descending, then column ascending.
 // LDS: 1 KiB of bins, 3 KiB of entries and a few counters, whatever n is.  Every branch around a barrier is uniform.
+//
+// SELF = 0 is nbmf_top_n's kernel (`self` is not read).  SELF = 1 is nbmf_neighbors' (nbmf_neighbors_kernels.inc; DESIGN.md
+// 4.16): column self[row] of the row is ineligible -- by index, whatever its value -- on top of the rest: the key of that
+// one entry is 0, and everything downstream is the same statements.
+template <int SELF>
 __global__ __launch_bounds__(TN_THREADS) void top_n_kernel(const double* __restrict__ panel, long long ldd, long long n,
                                                            const unsigned char* __restrict__ ex, long long ldx, int top,
-                                                           long long* __restrict__ out_cols, double* __restrict__ out_scores) {
+                                                           long long* __restrict__ out_cols, double* __restrict__ out_scores,
+                                                           const long long* __restrict__ self) {
   __shared__ unsigned long long ent_key[TN_MAX];
   __shared__ int ent_col[TN_MAX];
   __shared__ unsigned int hist[256];
@@ -190,7 +196,12 @@ __global__ __launch_bounds__(TN_THREADS) void top_n_kernel(const double* __restr
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const double* __restrict__ row = panel + (size_t)blockIdx.x * ldd;
   const unsigned char* __restrict__ exr = ex ? ex + (size_t)blockIdx.x * ldx : nullptr;
-  auto key_at = [&](long long j) { return top_n_key(row[j], exr && exr[j] != 0); };
+  long long self_j = -1;
+  if constexpr (SELF != 0) self_j = self[blockIdx.x];
+  auto key_at = [&](long long j) {
+    if constexpr (SELF != 0) return top_n_key(row[j], (exr && exr[j] != 0) || j == self_j);
+    else return top_n_key(row[j], exr && exr[j] != 0);   // (nbmf_top_n's statement, as it was)
+  };
 
   // 1. select
   unsigned long long prefix = 0, fixed = 0;   // the digits found so far, and the bits they occupy

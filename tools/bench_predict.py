@@ -44,6 +44,12 @@ that end in a synchronise (the library's predict calls do; NumPy's are synchrono
       slab by slab, np.argpartition of every slab, a merge and a sort; for N <= 256 also top_n(N) on every row plus a host
       merge.  The device result is compared for equality with the host selection over the device's own slabs before any
       time is taken; the digit passes and the device memory of every request are the library's own report (NBMF_PAIRS_TRACE).
+  (l) the items most similar to given items within one side of the matrix (``neighbors``; runs alone): Context.neighbors for
+      all 8192 features against the 8192 features, and for 8192 query samples (a seeded list) against all 65536 samples, at
+      N = 10 and N = 100 under each of the three metrics, median of five after a warm-up -- against the host route, timed once
+      in the same process: NumPy normalisation of the factor (for "profile" the Gram matrix and the two scaled operands),
+      ``A[:, query].T @ B``, the query's own column removed, np.argpartition and a sort of the N.  Before any time is taken
+      the device result is compared for EQUALITY with ``host_neighbors`` over the device's own slab (Context.similarity).
 
 The host legs are the comparison; the device path is never its own yardstick.  Before any time is taken the device and host
 results are compared at these sizes within tests/test_gpu_predict.py's bound, 2.1 K 2^-53 (|W| @ |H|) per entry; the
@@ -73,14 +79,14 @@ ap.add_argument("--rows", type=int, default=8192)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--legs", default="pairs,slabs,top_n,score_samples",
                 help="comma-separated: pairs, slabs, top_n, score_samples, theta_hist, rank_of, eval_curve, score_samples_bits, "
-                     "theta_hist_bits, top_n_bits, predict_bits, sample, hold_out, top_pairs")
+                     "theta_hist_bits, top_n_bits, predict_bits, sample, hold_out, top_pairs, neighbors")
 ap.add_argument("--device-only", action="store_true",
                 help="theta_hist, rank_of, predict_bits, sample: skip the timed host legs (for a kernel trace of the device legs)")
 args = ap.parse_args()
 legs = set(args.legs.split(","))
 BITS_LEGS = {"score_samples_bits", "theta_hist_bits", "top_n_bits"}
 DECISION_LEGS = {"predict_bits", "sample"}
-assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist", "rank_of", "eval_curve", "hold_out", "top_pairs"} | BITS_LEGS | DECISION_LEGS, f"unknown leg in {args.legs}"
+assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist", "rank_of", "eval_curve", "hold_out", "top_pairs", "neighbors"} | BITS_LEGS | DECISION_LEGS, f"unknown leg in {args.legs}"
 m, n, k, P, R = args.m, args.n, args.k, args.pairs, min(args.rows, args.m)
 
 
@@ -351,6 +357,102 @@ def top_pairs_leg():
             h["no_device_leg_loses"] = all(wins)
     return h
 
+
+def host_neighbors(S, top, self_idx):
+    """``host_neighbors`` of tests/test_neighbors_cpu.py -- score descending, ties by ascending index, ``self_idx[t]`` left
+    out of row t by index -- for a slab without NaN, a row block at a time: np.argpartition picks the candidates, and a row
+    whose ``top``-th score is tied with an entry outside them (the partition is then not the answer) is redone by np.lexsort
+    over the whole row."""
+    nq, L = S.shape
+    top = min(top, L - 1)
+    idx = np.empty((nq, top), dtype=np.int64)
+    sc = np.empty((nq, top))
+    for r0 in range(0, nq, 512):
+        blk = np.array(S[r0:r0 + 512])
+        ar = np.arange(blk.shape[0])
+        blk[ar, self_idx[r0:r0 + 512]] = -np.inf
+        cand = np.argpartition(-blk, top - 1, axis=1)[:, :top]
+        cs = blk[ar[:, None], cand]
+        order = np.lexsort((cand, -cs), axis=1)
+        cand, cs = np.take_along_axis(cand, order, 1), np.take_along_axis(cs, order, 1)
+        for t in np.nonzero((blk >= cs[:, -1:]).sum(1) != top)[0]:         # a tie across the cut
+            full = np.lexsort((np.arange(L), -blk[t]))[:top]
+            cand[t], cs[t] = full, blk[t, full]
+        idx[r0:r0 + 512], sc[r0:r0 + 512] = cand, cs
+    return idx, sc
+
+
+def neighbors_leg():
+    """(l): see the module docstring.  Its own factors-only context; ``--device-only`` skips the host route (for a kernel trace)."""
+    gn = np.random.default_rng(2030)
+    W = gn.uniform(0.1, 0.9, (k, m))
+    W /= W.sum(0, keepdims=True)
+    H = gn.uniform(0.05, 0.95, (k, n))
+    h = {}
+
+    def host_operands(F, C, metric):
+        if metric == "dot":
+            return F, F
+        if metric == "cosine":
+            Un = F / np.sqrt((F * F).sum(0))
+            return Un, Un
+        B = (C @ C.T) @ F
+        root = np.sqrt((F * B).sum(0))
+        return F / root, B / root
+
+    def host_route(F, C, metric, query, top):
+        A, B = host_operands(F, C, metric)
+        S = A[:, query].T @ B
+        S[np.arange(query.size), query] = -np.inf                          # the diagonal removed
+        cand = np.argpartition(-S, top - 1, axis=1)[:, :top]
+        cs = S[np.arange(query.size)[:, None], cand]
+        order = np.argsort(-cs, axis=1, kind="stable")
+        return np.take_along_axis(cand, order, 1), np.take_along_axis(cs, order, 1)
+
+    with _hip.Context(m, n, k) as ctx:
+        ctx.set_factors(W, H)
+        for name, axis, F, C in (("features", 1, H, W), ("samples", 0, W, H)):
+            L = F.shape[1]
+            query = np.arange(L) if L <= R else np.sort(gn.choice(L, R, replace=False))
+            e = {"items": int(L), "queries": int(query.size)}
+            for metric in ("dot", "cosine", "profile"):
+                t = {}
+                slab = ctx.similarity(axis=axis, metric=metric, query=query)
+                want = host_neighbors(slab, 100, query)
+                del slab
+                for N in (100, 10):
+                    got = ctx.neighbors(N, axis=axis, metric=metric, query=query)
+                    assert np.array_equal(got[0], want[0][:, :N]), f"{name} {metric} N = {N}: the ranking differs from the slab's"
+                    assert np.array_equal(got[1], want[1][:, :N]), f"{name} {metric} N = {N}: a score differs from the slab's"
+                    key = f"n{N}"
+                    t[key + "_device_s"], t[key + "_device_all_s"] = median_s(
+                        lambda: ctx.neighbors(N, axis=axis, metric=metric, query=query))
+                    say(f"neighbors {name} {metric} N = {N}: device {t[key + '_device_s']:.6f} s")
+                    if not args.device_only:
+                        t0 = time.perf_counter()
+                        host = host_route(F, C, metric, query, N)
+                        t[key + "_host_s"] = time.perf_counter() - t0
+                        t[key + "_host_agrees"] = float(np.mean(host[0] == got[0]))   # (another rounding: near-ties may swap)
+                        t[key + "_speedup"] = t[key + "_host_s"] / t[key + "_device_s"]
+                        t[key + "_device_wins"] = bool(t[key + "_device_s"] < t[key + "_host_s"])
+                        say(f"neighbors {name} {metric} N = {N}: host {t[key + '_host_s']:.6f} s, the same index in "
+                            f"{100 * t[key + '_host_agrees']:.4f} % of the slots")
+                t["similarity_s"], t["similarity_all_s"] = median_s(lambda: ctx.similarity(axis=axis, metric=metric, query=query))
+                say(f"similarity {name} {metric}: device slab to the host {t['similarity_s']:.6f} s")
+                e[metric] = t
+            h[name] = e
+    wins = [v for e in h.values() for t in e.values() if isinstance(t, dict) for key, v in t.items() if key.endswith("_device_wins")]
+    if wins:
+        h["no_device_leg_loses"] = all(wins)
+    return h
+
+
+if legs == {"neighbors"}:
+    res = {"tool": "bench_predict", "library": _hip.source_hash(), "shape": [m, n, k], "reps": args.reps, "slab_rows": R,
+           "neighbors_leg": neighbors_leg()}
+    print(json.dumps(res))
+    sys.exit(0)
+assert "neighbors" not in legs, "the neighbors leg runs alone: --legs neighbors"
 
 if legs == {"top_pairs"}:
     res = {"tool": "bench_predict", "library": _hip.source_hash(), "shape": [m, n, k], "reps": args.reps, "slab_rows": R,
