@@ -347,6 +347,46 @@ int nbmf_theta_hist_v(nbmf_ctx* ctx, int64_t row0, int64_t nrows, int bins,
                       const void* x, int x_kind, int64_t ldx, const void* mask, int mask_kind, int64_t ldmask,
                       int64_t* hist, int64_t* nan_count);
 
+/* Expected counts: the observed entries of the rows [row0, row0 + nrows) of the data, summed by (row, column group) and by
+ * column into the five integers that the expected count of ones under the model, its variance, the z-score of the observed
+ * count, the Brier score and Tjur's coefficient of discrimination are functions of.  theta[i, j] is bit for bit the entry
+ * nbmf_predict_rows(..., clip_theta = 1, NBMF_PREDICT_F64, ...) returns: the clip is always on, as in nbmf_theta_hist.  With
+ * Q = 2^NBMF_MOMENT_FRAC_BITS,
+ *   q1 = (int64) rint(theta * Q)             (the product is exact; rint rounds half to even)
+ *   q2 = (int64) rint((theta * theta) * Q)   (one rounded product, scaled exactly)
+ * -- NumPy: np.rint(theta * 2.0**32).astype(np.int64), np.rint((theta * theta) * 2.0**32).astype(np.int64).  An entry is
+ * OBSERVED as in nbmf_theta_hist (mask_kind NBMF_MASK_NONE, or its mask byte or bit nonzero).  An observed entry whose theta
+ * is not NaN adds to its slot
+ *   field 0  N_OBS    1                  field 2  S1       q1
+ *   field 1  N_ONES   x != 0             field 3  S2       q2                field 4  S1_ONES   x != 0 ? q1 : 0
+ * one whose theta is NaN adds 1 to nan_count[x != 0] (may be NULL) and nothing else.  The slots:
+ *   row_tab[((i - row0) * groups + g) * 5 + field]   g = col_group[j], where that is not -1 ("in no group"; col_group NULL:
+ *                                                    every column is in group 0); may be NULL
+ *   col_tab[j * 5 + field]                           over the call's rows, whatever column j's group; may be NULL (not both)
+ * So S1 / Q is the expected number of ones among a slot's observed entries, (S1 - S2) / Q its variance, N_ONES what was seen.
+ * x, mask, their kinds and leading dimensions are those of nbmf_theta_hist_v (x_kind NBMF_DATA_U8 or NBMF_DATA_BITS, mask_kind
+ * NBMF_MASK_NONE, NBMF_MASK_U8 or NBMF_MASK_BITS; nothing beyond column n - 1 is read; bits and bytes give identical arrays).
+ * Every sum is an exact integer: it does not depend on row0's alignment, on the panels (NBMF_PREDICT_PANEL_ROWS, as
+ * nbmf_predict_rows), on NBMF_MOMENT_COPIES (the copies of the column table the device spreads its adds over; default 32) or
+ * on the order the device adds in -- integer adds only, no floating-point atomics --; the same call twice gives the same
+ * arrays, and col_tab and nan_count of disjoint row ranges add up to those of their union.  A slot sums at most
+ * max(n, nrows) entries of at most Q each: nrows is at most 2^30 here and n is below 2^24 (what the product kernels launch),
+ * so no sum reaches 2^63.
+ * NBMF_ERR_ARG, with no output touched, for rows outside [0, m), nrows above 2^30, groups outside
+ * [1, NBMF_MOMENT_MAX_GROUPS], a label outside [-1, groups) (checked on the host before anything is launched), an unknown
+ * x_kind or mask_kind, a NULL mask with mask_kind set, a bad leading dimension, both tables NULL, or a NULL x with nrows > 0.
+ * nrows == 0 reads nothing and zero-fills col_tab and nan_count.  Same state rules and synchronisation as nbmf_predict_rows. */
+#define NBMF_MOMENT_MAX_GROUPS 16
+#define NBMF_MOMENT_FRAC_BITS 32
+#define NBMF_MOMENT_FIELDS 5   /* N_OBS, N_ONES, S1, S2, S1_ONES */
+int nbmf_moment_rows_v(nbmf_ctx* ctx, int64_t row0, int64_t nrows,
+                       const void* x, int x_kind, int64_t ldx,          /* NBMF_DATA_U8 | NBMF_DATA_BITS */
+                       const void* mask, int mask_kind, int64_t ldmask, /* NONE | U8 | BITS */
+                       const int32_t* col_group /* n labels in [-1, groups); NULL: every column in group 0 */, int groups,
+                       int64_t* row_tab /* [nrows][groups][5], may be NULL */,
+                       int64_t* col_tab /* [n][5], may be NULL (not both) */,
+                       int64_t* nan_count /* [2], may be NULL */);
+
 /* The best entries of Theta over the whole row range [row0, row0 + nrows), as ONE list of (row, column) pairs ranked on the
  * device: the global question nbmf_top_n (per row, at most NBMF_TOP_N_MAX slots) cannot answer.  theta[i, j] is bit for bit
  * the entry nbmf_predict_rows(..., clip_theta, NBMF_PREDICT_F64, ...) returns.  Two kinds of request:

@@ -4,9 +4,10 @@ Export list mirrors src/nbmf_mm/__init__.py:10-17 of the reference; ``PackedBits
 ``holdout_mask`` (the entries ``fit(holdout=...)`` holds out) are extensions.
 """
 from ._base import NBMF, NBMFMM, holdout_mask
+from ._metrics import Moments
 from ._packed import PackedBits
 from ._solver import nbmf_mm_solver
 
 __version__ = "0.1.0"
-# (``PackedBits`` and ``holdout_mask`` are importable from here but stay out of ``__all__``: the star-import surface is the reference's)
+# (``PackedBits``, ``holdout_mask`` and ``Moments`` (what ``NBMF.expected_counts`` returns) are importable from here but stay out of ``__all__``: the star-import surface is the reference's)
 __all__ = ["NBMFMM", "NBMF", "nbmf_mm_solver"]

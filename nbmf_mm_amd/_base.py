@@ -10,7 +10,7 @@ from sklearn.utils import check_array
 
 from . import _hip, _metrics
 from ._packed import PackedBits
-from ._solver import (device_neighbors, device_predict, device_rank_of, device_score, device_score_samples, device_theta_bits, device_theta_hist,
+from ._solver import (device_moments, device_neighbors, device_predict, device_rank_of, device_score, device_score_samples, device_theta_bits, device_theta_hist,
                       device_top_n, device_top_pairs, eval_pairs, holdout_args, nbmf_mm_restarts, nbmf_mm_solver, w_only_transform)
 from ._utils import check_is_fitted
 
@@ -617,6 +617,43 @@ class NBMFMM(BaseEstimator, TransformerMixin):
         if n_bins * resolution > _hip.HIST_MAX_BINS:
             raise ValueError(f"n_bins * resolution must be at most {_hip.HIST_MAX_BINS} (got {n_bins} * {resolution})")
         return _metrics.calibration_from_hist(self._theta_hist(X, mask, W, n_bins * resolution), n_bins)
+
+    # -- does the model reproduce the marginals: expected against observed counts on the device -----------
+    def expected_counts(self, X, mask=None, W=None, feature_groups=None, sample_groups=None):
+        """How many ones ``predict_proba(W)`` expects among the observed entries of the binary ``X`` -- per sample and
+        feature group, and per feature -- next to how many there are, summed on the GPU: ``(by_sample, by_feature)``, two
+        :class:`~nbmf_mm_amd.Moments`.  ``by_sample`` has shape ``(n_samples, n_feature_groups)``, or with
+        ``sample_groups`` ``(n_sample_groups, n_feature_groups)``; ``by_feature`` has shape ``(n_features,)``.  Each holds
+        the exact integer sums ``n_obs``, ``n_ones``, ``s1``, ``s2``, ``s1_ones`` of its slots and, as float64 properties,
+        ``expected`` (the expected number of ones), ``variance``, ``z = (n_ones - expected) / sqrt(variance)``,
+        ``mean_theta``, ``brier`` and ``tjur`` (the mean probability of the ones less that of the zeros).  This is the
+        degree / popularity check of a posterior-predictive check without drawing replicates, calibration by segment (is
+        a user segment over-predicted on an item category?), and observed-against-expected enrichment of a feature set
+        in a sample.  ``feature_groups`` / ``sample_groups``: integer 1-D arrays with one label ``>= -1`` per feature /
+        sample, ``n_*_groups = max label + 1``; None: one group of all features / every sample its own slot.  A feature
+        labelled -1 is in no column of ``by_sample`` and still has its entry of ``by_feature``; a sample labelled -1
+        counts nowhere, ``by_feature`` included (its mask is dropped on the host, one row block at a time, before the
+        block goes to the device).  ``X``, ``mask`` and ``W`` as in :meth:`theta_histogram`.  HELD-OUT USE:
+        ``fit(X, mask=train)``, then ``expected_counts(X, mask=held_out, ...)`` with ``held_out`` the complement of
+        ``train``: the counts over the entries the fit never saw.  The sums are exact integers: they do not depend on how
+        the input is streamed or grouped, or on the order the device adds in; more than 16 feature groups take one pass
+        over the matrix per 16.  Raises ``ValueError("Theta has NaN entries ...")`` if any observed Theta is NaN.  Only
+        ``5 (n_samples * n_feature_groups + n_features)`` integers leave the device."""
+        W, H = self._prediction_factors(W)
+        X, mask = self._scored_inputs(X, mask, W, H, exact=True)
+        flabels, n_fgroups = _hip.group_labels(feature_groups, H.shape[1], name="feature_groups")
+        keep = None
+        if sample_groups is not None:
+            slabels, n_sgroups = _hip.group_labels(sample_groups, W.shape[0], name="sample_groups")
+            keep = slabels >= 0
+        row_tab, col_tab, nan_count = device_moments(W, H, X, mask=mask, groups=None if feature_groups is None else flabels,
+                                                     n_groups=n_fgroups, keep_rows=keep, device=self.device)
+        if nan_count.any():
+            raise ValueError(f"Theta has NaN entries ({int(nan_count.sum())} of the observed ones): the factors are not finite")
+        by_sample = _metrics.Moments.from_table(row_tab)
+        if sample_groups is not None:
+            by_sample = by_sample.grouped(slabels, n_sgroups)
+        return by_sample, _metrics.Moments.from_table(col_tab)
 
 
 # alias kept for backwards compatibility (_base.py:269)

@@ -43,7 +43,7 @@ SYMBOLS = [
     "nbmf_rank_rows", "nbmf_set_eval", "nbmf_eval_loglik", "nbmf_get_eval", "nbmf_get_best_factors",
     "nbmf_top_n_v", "nbmf_score_rows_v", "nbmf_theta_hist_v", "nbmf_rank_rows_v", "nbmf_selftest_unpack_bits",
     "nbmf_theta_bits", "nbmf_hold_out", "nbmf_hold_out_undo", "nbmf_get_eval_pairs",
-    "nbmf_top_pairs", "nbmf_similarity", "nbmf_neighbors",
+    "nbmf_top_pairs", "nbmf_similarity", "nbmf_neighbors", "nbmf_moment_rows_v",
 ]
 DATA_F64, DATA_U8, DATA_F32, DATA_BITS = 0, 1, 2, 3
 PREDICT_F64, PREDICT_U8 = 0, 1
@@ -52,6 +52,10 @@ TOP_N_MAX = 256
 TOP_PAIRS_MAX = 1 << 22
 PAIRS_THETA, PAIRS_LIKELIHOOD = 0, 1
 HIST_MAX_BINS = 1024
+MOMENT_MAX_GROUPS = 16
+MOMENT_FRAC_BITS = 32
+#: the five sums of a slot of ``Context.moments``, in the order of the tables' last axis
+MOMENT_FIELDS = ("n_obs", "n_ones", "s1", "s2", "s1_ones")
 SIM_DOT, SIM_COSINE, SIM_PROFILE = 0, 1, 2
 #: the metric names of ``similarity`` / ``neighbors`` (``nbmf_similarity``)
 SIM_METRICS = {"dot": SIM_DOT, "cosine": SIM_COSINE, "profile": SIM_PROFILE}
@@ -214,6 +218,8 @@ def load():
     lib.nbmf_get_eval_pairs.argtypes = [c_void_p, c_int64, POINTER(c_int64), c_void_p, c_void_p, c_void_p]
     lib.nbmf_similarity.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64]
     lib.nbmf_neighbors.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64]
+    lib.nbmf_moment_rows_v.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_void_p, c_int,
+                                       c_void_p, c_void_p, c_void_p]
     for name in SYMBOLS:
         if name not in ("nbmf_last_error", "nbmf_source_hash"):
             getattr(lib, name).restype = c_int
@@ -351,6 +357,41 @@ def hist_bins(bins, name="bins"):
     if not 1 <= int(bins) <= HIST_MAX_BINS:
         raise ValueError(f"{name} must be in [1, {HIST_MAX_BINS}] (got {int(bins)})")
     return int(bins)
+
+
+def group_labels(groups, n, n_groups=None, name="groups", most=None):
+    """The labels of ``Context.moments`` (and of ``NBMF.expected_counts`` / ``Moments.grouped``) after the checks that need
+    no device: ``(labels, n_groups)``, ``labels`` C-contiguous int32.  ``groups`` is an integer (not bool) 1-D array of
+    length ``n`` with values ``>= -1``, -1 meaning "in no group"; None: everything in group 0.  ``n_groups`` defaults to
+    ``max label + 1`` (at least 1) and must be an integer above every label, and at most ``most`` where that is given.
+    Raises ``ValueError`` otherwise, naming the lowest offending position."""
+    if n_groups is not None:
+        if isinstance(n_groups, (bool, np.bool_)) or not isinstance(n_groups, (int, np.integer)) or n_groups < 1:
+            raise ValueError(f"n_{name} must be a positive integer (got {n_groups!r})")
+        n_groups = int(n_groups)
+    if groups is None:
+        labels = np.zeros(n, dtype=np.int32)
+    else:
+        g = np.asarray(groups)
+        if g.dtype == np.bool_ or not np.issubdtype(g.dtype, np.integer):
+            raise ValueError(f"{name} must be an integer array (got dtype {g.dtype})")
+        if g.shape != (n,):
+            raise ValueError(f"{name} must have shape ({n},) (got {g.shape})")
+        bad = np.flatnonzero(g < -1)
+        if bad.size:
+            raise ValueError(f"{name} label {int(g[bad[0]])} at position {int(bad[0])} is below -1")
+        top = int(g.max()) + 1 if g.size else 0
+        if n_groups is not None and top > n_groups:
+            at = int(np.flatnonzero(g >= n_groups)[0])
+            raise ValueError(f"{name} label {int(g[at])} at position {at} is outside [-1, {n_groups})")
+        if top > 2 ** 31 - 1:
+            raise ValueError(f"{name} labels must be below 2**31 - 1")
+        labels = np.ascontiguousarray(g, dtype=np.int32)
+    if n_groups is None:
+        n_groups = max(int(labels.max()) + 1 if labels.size else 0, 1)
+    if most is not None and n_groups > most:
+        raise ValueError(f"n_{name} must be at most {most} (got {n_groups})")
+    return labels, n_groups
 
 
 def csr_targets(indptr, indices, nrows, n):
@@ -852,6 +893,34 @@ class Context:
         _check(self._lib.nbmf_theta_hist_v(self._h, row0, nrows, bins, x.ctypes.data_as(c_void_p), x_kind, ldx, mptr, mkind, ldm,
                                            hist.ctypes.data_as(c_void_p), nan_count.ctypes.data_as(c_void_p)))
         return hist, nan_count
+
+    def moments(self, x, mask=None, groups=None, n_groups=None, row0=0, nrows=None, rows=True, cols=False):
+        """The observed entries of the rows ``[row0, row0 + nrows)`` of the binary data ``x``, summed on the device by
+        (row, column group) and / or by column (``nbmf_moment_rows_v``): ``(row_tab, col_tab, nan_count)``, int64 of shape
+        ``(nrows, n_groups, 5)``, ``(n, 5)`` and ``(2,)``; None for a table not asked for (``rows`` / ``cols``).  The last
+        axis is ``MOMENT_FIELDS``: the observed entries of the slot, the ones among them, ``S1 = sum rint(theta * 2**32)``,
+        ``S2 = sum rint((theta * theta) * 2**32)`` and S1 over the ones alone -- ``S1 / 2**32`` is the number of ones the
+        model expects in the slot and ``(S1 - S2) / 2**32`` its variance (:class:`~nbmf_mm_amd._metrics.Moments`).  An entry
+        whose Theta is NaN is counted in ``nan_count[x != 0]`` instead.  ``groups``: an integer array of ``n`` labels in
+        ``[-1, n_groups)``, -1 = in no group (such a column still counts in ``col_tab``); None: one group of all columns.
+        ``n_groups`` (default ``max label + 1``) is at most 16.  ``x`` and ``mask`` as in :meth:`theta_hist`: bool / uint8
+        of shape ``(nrows, n)``, slices of wider arrays are fine, or :class:`PackedBits` (the same arrays).  Theta is bit
+        for bit what :meth:`predict_rows` returns, clipped.  The sums are exact integers: the same whatever the panels and
+        the order of the device's additions, and ``col_tab`` of disjoint row ranges adds up."""
+        row0, nrows = self._rows(row0, nrows)
+        if not rows and not cols:
+            raise ValueError("nothing requested: rows and cols are both false")
+        labels, n_groups = group_labels(groups, self.n, n_groups, most=MOMENT_MAX_GROUPS)
+        x, x_kind, ldx = row_array(x, nrows, self.n, "x", BYTE_KINDS, packed=True)
+        mptr, mkind, ldm = self._mask_rows(mask, nrows)
+        row_tab = np.empty((nrows, n_groups, len(MOMENT_FIELDS)), dtype=np.int64) if rows else None
+        col_tab = np.empty((self.n, len(MOMENT_FIELDS)), dtype=np.int64) if cols else None
+        nan_count = np.empty(2, dtype=np.int64)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(c_void_p)   # noqa: E731
+        _check(self._lib.nbmf_moment_rows_v(self._h, row0, nrows, ptr(x), x_kind, ldx, mptr, mkind, ldm,
+                                            None if groups is None else ptr(labels), n_groups, ptr(row_tab), ptr(col_tab),
+                                            ptr(nan_count)))
+        return row_tab, col_tab, nan_count
 
     def top_pairs(self, top, kind="theta", x=None, mask=None, row0=0, nrows=None, clip_theta=True, return_scores=True):
         """The ``top`` best entries of Theta over ALL of the rows ``[row0, row0 + nrows)``, selected on the device

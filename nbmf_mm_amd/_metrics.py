@@ -7,6 +7,8 @@ from collections import namedtuple
 
 import numpy as np
 
+from ._hip import MOMENT_FIELDS, MOMENT_FRAC_BITS, group_labels
+
 
 def _hist(hist):
     hist = np.asarray(hist)
@@ -154,3 +156,128 @@ def ranking_from_ranks(ranks, k=10):
     pairs = (P[both] * (E[both] - P[both])).astype(np.float64)
     out["auc"] = _mean(1.0 - twice[both] / (2.0 * pairs))
     return out
+
+
+# ---- expected counts: the five integer sums of a slot and what follows from them -----------------------------
+def _exact_float(a):
+    """An integer array -- int64, or Python ints where a sum has outgrown int64 -- as float64, each entry rounded once."""
+    return np.asarray(a).astype(np.float64)
+
+
+class Moments(namedtuple("Moments", MOMENT_FIELDS)):
+    """The five integer sums of ``Context.moments`` / ``NBMF.expected_counts`` over the observed entries of each slot (a
+    sample, a feature, a sample group x feature group cell), as read-only arrays of one shape, and what follows from them.
+    With ``Q = 2**32`` and Theta the model's clipped probability of an entry:
+
+        n_obs    the observed entries of the slot                 s1       sum of rint(Theta * Q)
+        n_ones   the ones among them                              s2       sum of rint((Theta * Theta) * Q)
+                                                                  s1_ones  s1 over the ones alone
+
+    The arrays are int64; after :meth:`grouped` a field some sum of which has outgrown int64 is an object array of Python
+    ints instead -- the sums stay exact either way, and the float64 properties below are computed from the exact sums,
+    every integer difference taken before the one division:
+
+        expected    s1 / Q                     the number of ones the model expects among the slot's observed entries
+        variance    (s1 - s2) / Q              its variance: the sum of Theta (1 - Theta)
+        z           (n_ones - expected) / sqrt(variance)        NaN where variance <= 0 or n_obs == 0
+        mean_theta  expected / n_obs           NaN where nothing is observed
+        brier       (n_ones Q - 2 s1_ones + s2) / (Q n_obs)     the mean of (x - Theta)**2; NaN where nothing is observed
+        tjur        s1_ones / (Q n_ones) - (s1 - s1_ones) / (Q (n_obs - n_ones))    Tjur's coefficient of discrimination:
+                    the mean Theta of the ones less that of the zeros; NaN where a class is empty
+
+    ``expected`` is within ``n_obs * 2**-33`` of the sum of the slot's Thetas (the rounding of one entry's term)."""
+    __slots__ = ()
+    Q = 1 << MOMENT_FRAC_BITS
+
+    def __new__(cls, n_obs, n_ones, s1, s2, s1_ones):
+        fields = []
+        for name, a in zip(MOMENT_FIELDS, (n_obs, n_ones, s1, s2, s1_ones)):
+            a = np.array(a)                                   # (a copy: the holder's arrays are its own, and read-only)
+            if a.dtype != object:
+                if not np.issubdtype(a.dtype, np.integer):
+                    raise ValueError(f"{name} must be an integer array (got dtype {a.dtype})")
+                a = a.astype(object) if a.dtype == np.uint64 and a.size and int(a.max()) >= 1 << 63 else a.astype(np.int64)
+            if a.shape != np.shape(fields[0] if fields else a):
+                raise ValueError(f"{name} has shape {a.shape}, n_obs has {fields[0].shape}")
+            a.setflags(write=False)
+            fields.append(a)
+        return super().__new__(cls, *fields)
+
+    @classmethod
+    def from_table(cls, table):
+        """From an integer table whose last axis is the five fields (``Context.moments``' ``row_tab`` / ``col_tab``)."""
+        table = np.asarray(table)
+        if table.ndim < 1 or table.shape[-1] != len(MOMENT_FIELDS):
+            raise ValueError(f"the last axis of a moment table holds {len(MOMENT_FIELDS)} fields (got shape {table.shape})")
+        return cls(*(table[..., f] for f in range(len(MOMENT_FIELDS))))
+
+    @property
+    def shape(self):
+        return self.n_obs.shape
+
+    @property
+    def expected(self):
+        return _exact_float(self.s1) / self.Q
+
+    @property
+    def variance(self):
+        return _exact_float(self.s1 - self.s2) / self.Q
+
+    @property
+    def z(self):
+        var, seen = self.variance, _exact_float(self.n_obs) > 0
+        ok = (var > 0) & seen
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(ok, (_exact_float(self.n_ones) - self.expected) / np.sqrt(np.where(ok, var, 1.0)), np.nan)
+
+    @property
+    def mean_theta(self):
+        n = _exact_float(self.n_obs)
+        return np.where(n > 0, self.expected / np.where(n > 0, n, 1.0), np.nan)
+
+    @property
+    def brier(self):
+        n = _exact_float(self.n_obs)
+        # n_ones Q - 2 s1_ones + s2 as ONE exact integer: in int64 where no term or partial sum can leave it (slots of at
+        # most 2**29 ones and sums below 2**61: every table that came from the device ungrouped), else in Python ints
+        ones, s1o, s2 = (np.asarray(a) for a in (self.n_ones, self.s1_ones, self.s2))
+        small = all(a.dtype != object for a in (ones, s1o, s2)) and (
+            ones.size == 0 or (int(ones.max()) < (1 << 29) and int(s1o.max()) < (1 << 61) and int(s2.max()) < (1 << 61)))
+        if not small:
+            ones, s1o, s2 = (a.astype(object) for a in (ones, s1o, s2))
+        top = _exact_float(ones * self.Q - 2 * s1o + s2)
+        return np.where(n > 0, top / (self.Q * np.where(n > 0, n, 1.0)), np.nan)
+
+    @property
+    def tjur(self):
+        ones, zeros = _exact_float(self.n_ones), _exact_float(self.n_obs - self.n_ones)
+        ok = (ones > 0) & (zeros > 0)
+        of_ones = _exact_float(self.s1_ones) / (self.Q * np.where(ok, ones, 1.0))
+        of_zeros = _exact_float(self.s1 - self.s1_ones) / (self.Q * np.where(ok, zeros, 1.0))
+        return np.where(ok, of_ones - of_zeros, np.nan)
+
+    def grouped(self, labels, n_groups=None):
+        """The slots summed along the LEADING axis into groups: ``labels`` holds one integer per leading index, in
+        ``[-1, n_groups)``, and -1 drops the slot (``n_groups`` defaults to ``max label + 1``); the result has ``n_groups``
+        in place of the leading axis.  Exact whatever the sums reach: every field is split into its high and low 32 bits,
+        the halves are summed as int64 (at most 2**31 slots of less than 2**32 each) and put together as Python ints; a
+        field all of whose sums fit int64 comes back as int64, another as an object array of Python ints."""
+        if not self.shape:
+            raise ValueError("grouped needs a leading axis to sum over")
+        labels, n_groups = group_labels(labels, self.shape[0], n_groups, name="labels")
+        keep = labels >= 0
+        out = []
+        for a in self:
+            if a.dtype == object:                             # (already beyond int64: Python ints all the way)
+                total = np.zeros((n_groups,) + a.shape[1:], dtype=object)
+                np.add.at(total, labels[keep], a[keep])
+            else:
+                hi, lo = np.zeros((2, n_groups) + a.shape[1:], dtype=np.int64)
+                np.add.at(hi, labels[keep], a[keep] >> 32)
+                np.add.at(lo, labels[keep], a[keep] & 0xffffffff)
+                if hi.size == 0 or int(hi.max()) < (1 << 30):  # hi * 2**32 + lo < 2**63: int64 holds it
+                    total = (hi << 32) + lo
+                else:
+                    total = hi.astype(object) * (1 << 32) + lo.astype(object)
+            out.append(total)
+        return Moments(*out)

@@ -623,3 +623,48 @@ def device_theta_hist(W, H, X, mask=None, bins=256, device=0):
             hist += h
             nan_count += c
     return hist, nan_count
+
+
+def device_moments(W, H, X, mask=None, groups=None, n_groups=None, keep_rows=None, device=0, _pass_groups=_hip.MOMENT_MAX_GROUPS):
+    """The observed entries of the binary ``X``, summed on the GPU (``Context.moments``) into the five integers per slot
+    that the expected count of ones under Theta = clip(``W @ H``, 0, 1), its variance and the observed count are functions of:
+    ``(row_tab int64 (rows, n_groups, 5), col_tab int64 (features, 5), nan_count int64 (2,))``.  ``W``, ``H`` as in
+    :func:`device_predict`; ``X`` and ``mask`` as in :func:`device_theta_hist`, already validated; ``groups`` / ``n_groups``
+    the feature labels, already validated (``_hip.group_labels``; any number of groups).  Factors only: no context holds
+    the data.  Dense bool / uint8 input with a bool / uint8 (or no) mask and every :class:`PackedBits` goes to the device as
+    it is, in one call per pass; anything else goes in row blocks of at most ``SCORE_SAMPLES_BLOCK_BYTES`` made dense
+    one at a time.  The blocks' column sums are added on the host as int64: integers, so block-streamed input gives
+    exactly the arrays of the one-call form.  More than ``MOMENT_MAX_GROUPS`` groups run in passes of that many labels
+    each (``_pass_groups``: a test hook), the other labels set to -1, and the row tables are put side by side -- a slot's
+    sum does not depend on the passes; the column table and the NaN counts are those of the first pass (they do not look
+    at the groups).  ``keep_rows`` (bool per row, None: all): the rows that are False count nowhere -- their mask is
+    dropped on the host, one row block at a time (such a request is block-streamed) -- and their ``row_tab`` is zero."""
+    X, mask, one_call = _sliceable(X, mask)
+    if keep_rows is not None and np.all(keep_rows):
+        keep_rows = None
+    labels, n_groups = _hip.group_labels(groups, H.shape[1], n_groups)
+    with _factors_only(W, H, device) as (ctx, m, n):
+        one_call = one_call and keep_rows is None
+        block = m if one_call else max(16, SCORE_SAMPLES_BLOCK_BYTES // (8 * max(n, 1)) // 16 * 16)
+        row_tab = np.zeros((m, n_groups, len(_hip.MOMENT_FIELDS)), dtype=np.int64)
+        col_tab = np.zeros((n, len(_hip.MOMENT_FIELDS)), dtype=np.int64)
+        nan_count = np.zeros(2, dtype=np.int64)
+        for r0 in range(0, m, max(block, 1)):
+            nr = min(block, m - r0)
+            x = _row_block(X, r0, nr, False)
+            if not isinstance(x, PackedBits) and x.dtype == np.float64:
+                raise ValueError("X must be binary")
+            mk = None if mask is None else _row_block(mask, r0, nr, True)
+            if keep_rows is not None and not np.all(keep_rows[r0:r0 + nr]):
+                mk = np.ones((nr, n), dtype=bool) if mk is None else np.array(mk.toarray() if isinstance(mk, PackedBits) else mk) != 0
+                mk[~keep_rows[r0:r0 + nr]] = False
+            for g0 in range(0, n_groups, _pass_groups):
+                ng = min(_pass_groups, n_groups - g0)
+                part = labels if ng == n_groups else np.where((labels >= g0) & (labels < g0 + ng), labels - g0, -1)
+                rt, ct, nc = ctx.moments(x, mk, groups=None if groups is None else part, n_groups=ng, row0=r0, nrows=nr,
+                                         rows=True, cols=g0 == 0)
+                row_tab[r0:r0 + nr, g0:g0 + ng] = rt
+                if g0 == 0:
+                    col_tab += ct
+                    nan_count += nc
+    return row_tab, col_tab, nan_count

@@ -322,6 +322,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 #include "nbmf_predict_kernels.inc"
 #include "nbmf_score_kernels.inc"
 #include "nbmf_hist_kernels.inc"
+#include "nbmf_moment_kernels.inc"
 #include "nbmf_pairs_kernels.inc"
 #include "nbmf_rank_kernels.inc"
 #include "nbmf_eval_kernels.inc"
@@ -2695,6 +2696,19 @@ hipError_t launch_hist_panel(nbmf_ctx* c, const RowPanels& pl, long long p0, lon
   return hipGetLastError();
 }
 
+// The same rows of Theta, clipped, summed by (row, column group) and by column against the staged data and mask panels
+// (nbmf_moment_rows_v).  rtab_d (this panel's table, zeroed by the caller) or ctab_d may be null.
+hipError_t launch_moment_panel(nbmf_ctx* c, const RowPanels& pl, long long p0, long long pn, int groups, const unsigned char* x_d,
+                               const unsigned char* m_d, const int* grp_d, unsigned long long* rtab_d, int copies,
+                               unsigned long long* ctab_d, unsigned long long* nan_d) {
+  // a table of 16 rows x groups slots per wave: <= 32 KiB
+  const size_t lds = rtab_d ? sizeof(unsigned long long) * PR_WAVES * 16 * (size_t)groups * MO_WORDS : 0;
+  hipLaunchKernelGGL(moment_rows_kernel, pl.grid(p0, pn), dim3(PR_WAVES * 64), lds, c->stream, (const double*)c->Wn,
+                     (const double*)c->Hn, c->k, (long long)c->mA, (long long)c->nA, (long long)c->n, p0, pn, pl.ldp, groups, x_d, m_d,
+                     grp_d, rtab_d, copies, ctab_d, nan_d);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -4256,6 +4270,91 @@ int nbmf_theta_hist_v(nbmf_ctx* c, int64_t row0, int64_t nrows, int bins, const 
   int64_t nan[2] = {0, 0};
   HIPCHK(hipMemcpyAsync(hist, sum_d, sizeof(int64_t) * slots, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(nan, sum_d + slots, sizeof nan, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (nan_count) nan_count[0] = nan[0], nan_count[1] = nan[1];
+  return NBMF_OK;
+}
+
+// ---- Theta summed against data: expected counts by (row, column group) and by column (nbmf_moment_kernels.inc)
+// nbmf_theta_hist_v's walk: per panel the caller's data and mask rows up into staging panels, then the fused
+// product-and-sum kernel.  The panel's row table is zeroed before the launch and comes down after it; the column table
+// (NBMF_MOMENT_COPIES copies of it -- environment; default 32, fewer where n is so large that they would pass 64 MiB --
+// which theta_hist_finish_kernel adds up at the end) and the NaN counts stay on the device for the whole call.  The labels
+// go up once, padded to nA entries with -1.  Integer adds: the panels need no alignment.
+int nbmf_moment_rows_v(nbmf_ctx* c, int64_t row0, int64_t nrows, const void* x, int x_kind, int64_t ldx, const void* mask, int mask_kind,
+                       int64_t ldmask, const int32_t* col_group, int groups, int64_t* row_tab, int64_t* col_tab, int64_t* nan_count) {
+  if (int rc = predict_ready(c)) return rc;
+  if (int rc = check_rows(c, row0, nrows)) return rc;
+  if (nrows > (1ll << 30)) return fail(NBMF_ERR_ARG, "nrows must be at most 2^30 (got %lld)", (long long)nrows);
+  if (groups < 1 || groups > NBMF_MOMENT_MAX_GROUPS)
+    return fail(NBMF_ERR_ARG, "groups must be in [1, %d] (got %d)", NBMF_MOMENT_MAX_GROUPS, groups);
+  if (x_kind != NBMF_DATA_U8 && x_kind != NBMF_DATA_BITS) return fail(NBMF_ERR_ARG, "unknown x_kind %d", x_kind);
+  if (mask_kind != NBMF_MASK_NONE && mask_kind != NBMF_MASK_U8 && mask_kind != NBMF_MASK_BITS)
+    return fail(NBMF_ERR_ARG, "unknown mask_kind %d", mask_kind);
+  if (mask_kind != NBMF_MASK_NONE && !mask) return fail(NBMF_ERR_ARG, "mask_kind set but mask is NULL");
+  if (mask_kind == NBMF_MASK_NONE) mask = nullptr;
+  const bool xbits = x_kind == NBMF_DATA_BITS, mbits = mask_kind == NBMF_MASK_BITS;
+  if (int rc = check_row_ld("ldx", ldx, xbits, c->n)) return rc;
+  if (mask)
+    if (int rc = check_row_ld("ldmask", ldmask, mbits, c->n)) return rc;
+  if (!row_tab && !col_tab) return fail(NBMF_ERR_ARG, "no output requested");
+  if (nrows > 0 && !x) return fail(NBMF_ERR_ARG, "null data");
+  const long long n = c->n, ldp = panel_ld(c);
+  if (col_group)
+    for (long long j = 0; j < n; ++j)
+      if (col_group[j] < -1 || col_group[j] >= groups)
+        return fail(NBMF_ERR_ARG, "the group of column %lld is %d, outside [-1, %d)", j, (int)col_group[j], groups);
+  static_assert(MO_FIELDS == NBMF_MOMENT_FIELDS && sizeof(int64_t) == sizeof(unsigned long long), "the tables come down as they are");
+  const size_t row_words = (size_t)groups * MO_FIELDS, col_words = (size_t)n * MO_FIELDS;
+  RowPanels pl;
+  const size_t bit_bytes = (size_t)packed_ld(n) * ((xbits ? 1 : 0) + (mbits ? 1 : 0));   // the packed rows as they came
+  const size_t per_row = (size_t)ldp * (mask ? 2 : 1) + bit_bytes + (row_tab ? sizeof(int64_t) * row_words : 0);
+  if (int rc = plan_row_panels(c, "nbmf_moment_rows", row0, nrows, per_row, false, &pl)) return rc;
+  if (col_tab) std::fill(col_tab, col_tab + (size_t)n * MO_FIELDS, (int64_t)0);   // (nrows == 0: nothing is read; the sums over no rows)
+  if (nan_count) nan_count[0] = nan_count[1] = 0;
+  if (nrows == 0) return NBMF_OK;
+  if (int rc = set_device(c)) return rc;
+  std::vector<int> labels((size_t)c->nA, -1);   // (the pad columns: in no group)
+  for (long long j = 0; j < n; ++j) labels[(size_t)j] = col_group ? (int)col_group[j] : 0;
+  const long long fit = std::max<long long>(1, (long long)((64ull << 20) / (sizeof(int64_t) * col_words)));
+  const int copies = (int)std::min<long long>(fit, std::min<long long>(1024, std::max<long long>(1, env_int("NBMF_MOMENT_COPIES", 32))));
+  PredictStage st{c->stream, {}};
+  unsigned char *x_d = nullptr, *m_d = nullptr, *xbits_d = nullptr, *mbits_d = nullptr;
+  int* grp_d = nullptr;
+  unsigned long long *rtab_d = nullptr, *ctab_d = nullptr, *csum_d = nullptr, *nan_d = nullptr;
+  HIPCHK(st.get(&x_d, (size_t)pl.stage_rows() * ldp));
+  if (mask) HIPCHK(st.get(&m_d, (size_t)pl.stage_rows() * ldp));
+  if (xbits) HIPCHK(st.get(&xbits_d, (size_t)pl.stage_rows() * packed_ld(n)));
+  if (mbits) HIPCHK(st.get(&mbits_d, (size_t)pl.stage_rows() * packed_ld(n)));
+  HIPCHK(st.get(&grp_d, sizeof(int) * labels.size()));
+  HIPCHK(st.get(&nan_d, sizeof(unsigned long long) * 2));
+  if (row_tab) HIPCHK(st.get(&rtab_d, sizeof(unsigned long long) * (size_t)pl.stage_rows() * row_words));
+  if (col_tab) {
+    HIPCHK(st.get(&ctab_d, sizeof(unsigned long long) * col_words * copies));
+    HIPCHK(st.get(&csum_d, sizeof(unsigned long long) * col_words));
+    HIPCHK(hipMemsetAsync(ctab_d, 0, sizeof(unsigned long long) * col_words * copies, c->stream));
+  }
+  HIPCHK(hipMemsetAsync(nan_d, 0, sizeof(unsigned long long) * 2, c->stream));
+  HIPCHK(hipMemcpyAsync(grp_d, labels.data(), sizeof(int) * labels.size(), hipMemcpyHostToDevice, c->stream));
+  for (long long p0 = row0, pn; p0 < pl.end; p0 += pn) {
+    pn = pl.rows_at(p0);
+    const size_t done = (size_t)(p0 - row0);
+    HIPCHK(stage_rows_as_bytes(xbits_d, (const char*)x + done * ldx, xbits, 1, ldx, n, pn, x_d, ldp, c->stream));
+    if (mask) HIPCHK(stage_rows_as_bytes(mbits_d, (const char*)mask + done * ldmask, mbits, 1, ldmask, n, pn, m_d, ldp, c->stream));
+    if (row_tab) HIPCHK(hipMemsetAsync(rtab_d, 0, sizeof(unsigned long long) * (size_t)pn * row_words, c->stream));
+    HIPCHK(launch_moment_panel(c, pl, p0, pn, groups, x_d, m_d, grp_d, rtab_d, copies, ctab_d, nan_d));
+    if (row_tab)
+      HIPCHK(hipMemcpyAsync(row_tab + done * row_words, rtab_d, sizeof(int64_t) * (size_t)pn * row_words, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the next panel reuses the staging)
+  }
+  if (col_tab) {
+    hipLaunchKernelGGL(theta_hist_finish_kernel, dim3((unsigned)((col_words + 255) / 256)), dim3(256), 0, c->stream,
+                       (const unsigned long long*)ctab_d, copies, (int)col_words, csum_d);   // (n < 2^24: col_words fits an int)
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(col_tab, csum_d, sizeof(int64_t) * col_words, hipMemcpyDeviceToHost, c->stream));
+  }
+  int64_t nan[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(nan, nan_d, sizeof nan, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (nan_count) nan_count[0] = nan[0], nan_count[1] = nan[1];
   return NBMF_OK;

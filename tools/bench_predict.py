@@ -50,13 +50,20 @@ that end in a synchronise (the library's predict calls do; NumPy's are synchrono
       in the same process: NumPy normalisation of the factor (for "profile" the Gram matrix and the two scaled operands),
       ``A[:, query].T @ B``, the query's own column removed, np.argpartition and a sort of the N.  Before any time is taken
       the device result is compared for EQUALITY with ``host_neighbors`` over the device's own slab (Context.similarity).
+  (m) expected counts by (row, feature group) and by feature over those rows (``moments``): the rows, data and 90 % mask of
+      (e); Context.moments, both tables, with one group, with 16 groups in contiguous runs and with 16 groups drawn at
+      random (the unfavourable layout: every wave flushes all 16 slots of each of its rows), from uint8 and from packed
+      bits, with and without the mask -- against the host route there was before it (predict_rows float64, then the five
+      sums per slot in float64 NumPy: masked copies and matrix products with the one-hot group matrix), and beside
+      Context.theta_hist at 1024 bins on the same operands in the same process.  The tables are compared for EQUALITY with
+      the integer contract in NumPy over the device's own slab before any time is taken.
 
 The host legs are the comparison; the device path is never its own yardstick.  Before any time is taken the device and host
 results are compared at these sizes within tests/test_gpu_predict.py's bound, 2.1 K 2^-53 (|W| @ |H|) per entry; the
 ranking is compared exactly with the host selection over the device's own slab (the shape has no ties); the score sums are
 compared with the host's over the device's own slab within tests/test_gpu_score_samples.py's bound plus NumPy's own
 summation error; the class histograms and the ranks are compared for EQUALITY with NumPy's over the device's own slab.
-``--legs`` picks the legs to time (default: the first four; ``theta_hist``, ``rank_of``, ``eval_curve`` and the ``*_bits`` legs are
+``--legs`` picks the legs to time (default: the first four; ``theta_hist``, ``moments``, ``rank_of``, ``eval_curve`` and the ``*_bits`` legs are
 asked for by name, as are ``predict_bits`` and ``sample``; ``eval_curve`` alone, or ``hold_out`` alone, skips the factors-only
 context and its agreement checks).
 Prints progress lines and, last, ONE JSON line.  Needs an MI355X: there is no CPU fallback."""
@@ -79,14 +86,14 @@ ap.add_argument("--rows", type=int, default=8192)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--legs", default="pairs,slabs,top_n,score_samples",
                 help="comma-separated: pairs, slabs, top_n, score_samples, theta_hist, rank_of, eval_curve, score_samples_bits, "
-                     "theta_hist_bits, top_n_bits, predict_bits, sample, hold_out, top_pairs, neighbors")
+                     "theta_hist_bits, top_n_bits, predict_bits, sample, hold_out, top_pairs, neighbors, moments")
 ap.add_argument("--device-only", action="store_true",
-                help="theta_hist, rank_of, predict_bits, sample: skip the timed host legs (for a kernel trace of the device legs)")
+                help="theta_hist, moments, rank_of, predict_bits, sample: skip the timed host legs (for a kernel trace of the device legs)")
 args = ap.parse_args()
 legs = set(args.legs.split(","))
 BITS_LEGS = {"score_samples_bits", "theta_hist_bits", "top_n_bits"}
 DECISION_LEGS = {"predict_bits", "sample"}
-assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist", "rank_of", "eval_curve", "hold_out", "top_pairs", "neighbors"} | BITS_LEGS | DECISION_LEGS, f"unknown leg in {args.legs}"
+assert legs <= {"pairs", "slabs", "top_n", "score_samples", "theta_hist", "rank_of", "eval_curve", "hold_out", "top_pairs", "neighbors", "moments"} | BITS_LEGS | DECISION_LEGS, f"unknown leg in {args.legs}"
 m, n, k, P, R = args.m, args.n, args.k, args.pairs, min(args.rows, args.m)
 
 
@@ -768,6 +775,82 @@ with _hip.Context(m, n, k) as ctx:
                 t["speedup_vs_best_host_route"] = best / t["device_s"]
             f[f"T{T}"] = t
         res["rank_of_leg"] = f
+
+    # ---- (m) expected counts by (row, feature group) and by feature (before (e), which replaces the factors) ------------------
+    if "moments" in legs:
+        from nbmf_mm_amd import PackedBits
+        gh = np.random.default_rng(2025)                    # the stream of (e): the same data and mask
+        X = gh.random((R, n)) < 0.25
+        mask = gh.random((R, n)) < 0.90
+        PX, PM = PackedBits.from_dense(X), PackedBits.from_dense(mask)
+        gm = np.random.default_rng(2029)
+        layouts = {"G1": (None, 1), "G16_runs": (np.arange(n) * 16 // n, 16), "G16_random": (gm.integers(0, 16, n), 16)}
+
+        def exact_terms(mk):
+            """The five integer terms of every entry under the contract, in NumPy over the device's own slab."""
+            theta = ctx.predict_rows(0, R, out=out64)
+            obs = np.ones((R, n), dtype=bool) if mk is None else mk
+            q1 = np.rint(theta * 2.0 ** 32).astype(np.int64)
+            q2 = np.rint((theta * theta) * 2.0 ** 32).astype(np.int64)
+            return (obs.astype(np.int64), (obs & X).astype(np.int64), np.where(obs, q1, 0), np.where(obs, q2, 0), np.where(obs & X, q1, 0))
+
+        def exact_tables(terms, groups, G):
+            lab = np.zeros(n, dtype=np.int64) if groups is None else groups
+            rows_ = np.stack([np.stack([t[:, lab == g].sum(1) for g in range(G)], axis=1) for t in terms], axis=-1)
+            return rows_, np.stack([t.sum(0) for t in terms], axis=-1)
+
+        def host_float(groups, G, mk):
+            """predict_rows, then the five sums per slot in float64: what a user had before the device call."""
+            theta = ctx.predict_rows(0, R, out=out64)
+            obs = np.ones((R, n), dtype=bool) if mk is None else mk
+            onehot = np.zeros((n, G))
+            onehot[np.arange(n), 0 if groups is None else groups] = 1.0
+            t = np.where(obs, theta, 0.0)
+            terms = (obs.astype(np.float64), (obs & X).astype(np.float64), t, t * t, np.where(X, t, 0.0))
+            return [a @ onehot for a in terms], [a.sum(0) for a in terms]
+
+        mo = {"data": "uint8 and bits", "observed": float(mask.mean()), "input_bytes_uint8": 2 * R * n,
+              "output_bytes": {name: 8 * 5 * (R * G + n) + 16 for name, (_, G) in layouts.items()}}
+        for mk in () if args.device_only else (mask, None):  # (a trace run skips the host's half minute of integer NumPy)
+            terms = exact_terms(mk)
+            for name, (groups, G) in layouts.items():
+                row_tab, col_tab, nan_count = ctx.moments(X, mk, groups=groups, n_groups=G, row0=0, nrows=R, cols=True)
+                want_rows, want_cols = exact_tables(terms, groups, G)
+                assert np.array_equal(row_tab, want_rows) and np.array_equal(col_tab, want_cols) and not nan_count.any(), \
+                    f"moments ({name}) disagrees with NumPy over predict_rows"
+            del terms, want_rows, want_cols
+        for name, (groups, G) in layouts.items():
+            got = ctx.moments(PX, PM, groups=groups, n_groups=G, row0=0, nrows=R, cols=True)
+            want = ctx.moments(X, mask, groups=groups, n_groups=G, row0=0, nrows=R, cols=True)
+            assert all(np.array_equal(a, b) for a, b in zip(got, want)), f"moments ({name}) from bits differs from uint8"
+        for name, (groups, G) in layouts.items():
+            for tag, x, mk, kw in (("uint8", X, mask, {}), ("bits", PX, PM, {}), ("uint8_no_mask", X, None, {}),
+                                   ("uint8_rows_only", X, mask, {"cols": False}), ("uint8_cols_only", X, mask, {"rows": False})):
+                key = f"{name}_{tag}"
+                call = lambda: ctx.moments(x, mk, groups=groups, n_groups=G, row0=0, nrows=R, **{"cols": True, **kw})   # noqa: E731
+                mo[key + "_s"], mo[key + "_all_s"] = median_s(call)
+                say(f"moments {key}", mo[key + "_s"])
+            # the two byte panels differ by one with and without the mask: twice the difference estimates the upload's share
+            mo[name + "_upload_share_estimated"] = min(1.0, 2.0 * max(0.0, mo[name + "_uint8_s"] - mo[name + "_uint8_no_mask_s"]) / mo[name + "_uint8_s"])
+        for copies in ("1", "4", "32", "256"):
+            os.environ["NBMF_MOMENT_COPIES"] = copies
+            groups, G = layouts["G16_random"]
+            mo[f"G16_random_uint8_copies_{copies}_s"], _ = median_s(lambda: ctx.moments(X, mask, groups=groups, n_groups=G, row0=0, nrows=R, cols=True))
+            say(f"moments G16_random uint8 copies {copies}", mo[f"G16_random_uint8_copies_{copies}_s"])
+        del os.environ["NBMF_MOMENT_COPIES"]
+        mo["theta_hist_1024_uint8_s"], mo["theta_hist_1024_uint8_all_s"] = median_s(lambda: ctx.theta_hist(X, mask, 0, R, bins=1024))
+        say("theta_hist 1024 bins uint8 (the same operands)", mo["theta_hist_1024_uint8_s"])
+        mo["theta_hist_1024_bits_s"], _ = median_s(lambda: ctx.theta_hist(PX, PM, 0, R, bins=1024))
+        say("theta_hist 1024 bins bits", mo["theta_hist_1024_bits_s"])
+        mo["predict_rows_f64_s"], _ = median_s(lambda: ctx.predict_rows(0, R, out=out64))
+        say("predict_rows float64 (the slab the host route starts from)", mo["predict_rows_f64_s"])
+        if not args.device_only:
+            for name, (groups, G) in layouts.items():
+                mo[name + "_predict_rows_then_numpy_s"], mo[name + "_predict_rows_then_numpy_all_s"] = median_s(lambda: host_float(groups, G, mask))
+                say(f"{name} predict_rows + NumPy float sums", mo[name + "_predict_rows_then_numpy_s"])
+                mo[name + "_speedup_vs_predict_rows_then_numpy"] = mo[name + "_predict_rows_then_numpy_s"] / mo[name + "_uint8_s"]
+        res["moments_leg"] = mo
+        del X, mask, PX, PM
 
     # ---- (e) class histograms of Theta ------------------------------------------------------------------------------------------
     if "theta_hist" in legs:
